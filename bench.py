@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """bench.py -- pairs/s of the contrastive image/video-text training step on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload l14|b16|vtp8|vtp8t|dmae12]      (N > 1: starts its own N ranks under torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--workload l14|b16|vtp8|vtp8t|dmae12] [--full] [--dump-outputs DIR]
+                                                                                          (N > 1: starts its own N ranks under torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Default workload `l14` (the BASELINE metric): one step = forward + backward + optimizer over one synthetic batch already resident in
@@ -20,7 +21,10 @@ Other workloads (BASELINE.json configs 1, 3, 4; their own metric strings, never 
           + WTI scores + CrossEn in both directions (TPM-CL off)
   dmae12  prj/dmae_vtp `univl`, 12 frames, 30-word captions, stage1 + stage3 (seqTransf temporal transformer, WTI similarity, NegNCE, TPM-CL type 4)
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the contract fields (`value` = pairs/s over the timed
+steps, `ms_per_step`).  --dump-outputs DIR also writes what the last timed step computed (loss, meters, a fixed seeded sample of the updated fp32
+master weights and AdamW first moments) as DIR/<name>.npy; the inputs and the initial weights are seeded, identical from run to run.
+With --full the line also holds (null otherwise; --gemm-table turns the GEMM trace and `roofline` on by itself)
   roofline      the dominant kernel family (the bf16 MFMA GEMMs): algorithmic flops per launch / average launch duration, measured live
                 with HIP events on the launch stream over the timed steps; peak = 2.5 PFLOP/s dense bf16 (MI355X_MICROARCH.md)
   cpu_baseline  the CPU oracle (oracle/, plain torch fp32 restatement of the reference; kind "port") timed on this host's cores on a bounded
@@ -170,10 +174,13 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="l14", choices=sorted(list(M2_WORKLOADS) + list(VTP_WORKLOADS)))
     ap.add_argument("--batch", type=int, default=None, help="pairs per GPU (default: 1024 for the M2 workloads, 64 / 128 videos for vtp8 / dmae12)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: the GEMM roofline (per-launch HIP events over "
+                                                         "the timed steps + a clock probe) and the CPU-oracle baseline (N = 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU-oracle baseline out")
     ap.add_argument("--recompute-ffn-norm", action="store_true", help="do not keep ffn_layernorm(gelu(u)) for backward (saves ~65 GiB at 1024 pairs/GPU, costs ~3 %%)")
-    ap.add_argument("--gemm-table", default=None, help="write per-shape GEMM timing (from the live HIP-event trace) to this file")
+    ap.add_argument("--gemm-table", default=None, help="write per-shape GEMM timing (from the live HIP-event trace, which this turns on) to this file")
     ap.add_argument("--cpu-sample", type=int, default=2, help="pairs per pass of the CPU-oracle sample")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32)")
     return ap.parse_args()
 
 
@@ -452,6 +459,26 @@ def _gemm_clock_mhz(device):
         return None
 
 
+def dump_outputs(trainer, loss, meters, out_dir, sample=1 << 22):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files -- the loss it returned, its meters (the loss terms), and the
+    fp32 master weights and AdamW first moments it updated, at a fixed seeded sample of arena positions (the same positions in every run): 2 x 16 MiB."""
+    import re
+
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss.detach().float().reshape(()).cpu()}
+    for k, v in meters.items():
+        arrays["meter_" + re.sub(r"\W", "_", k)] = torch.tensor(v, dtype=torch.float32)
+    master, exp_avg = trainer.arena.master, trainer.optimizer.exp_avg
+    n = master.numel()
+    idx = torch.randint(0, n, (min(n, sample),), generator=torch.Generator().manual_seed(0)).sort().values.to(master.device)
+    arrays["master_weights_sample"] = master[idx].cpu()
+    arrays["adam_exp_avg_sample"] = exp_avg[idx].cpu()
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.numpy().astype(np.float32))
+
+
 def main():
     a = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -501,7 +528,9 @@ def main():
     if world > 1:
         dist.barrier()
     hw.sync()
-    ops.GEMM_TRACE = None if hw.dry else []   # (HIP events on the launch stream: none on the host)
+    want_roofline = a.full or a.gemm_table is not None
+    trace_gemms = want_roofline and not hw.dry   # (HIP events on the launch stream: none on the host)
+    ops.GEMM_TRACE = [] if trace_gemms else None
     t0 = time.perf_counter()
     for _ in range(a.steps):
         loss = step()
@@ -517,7 +546,9 @@ def main():
         elapsed = float(t)
     final_loss = float(loss.detach())
     meters = trainer.read_meters()
-    gemm_clock_mhz = _gemm_clock_mhz(device) if rank == 0 and not hw.dry else None
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(trainer, loss, meters, a.dump_outputs)
+    gemm_clock_mhz = _gemm_clock_mhz(device) if rank == 0 and trace_gemms else None
 
     if rank == 0:
         ms = elapsed / a.steps * 1e3
@@ -545,7 +576,7 @@ def main():
         # (tools/gpu_traffic.sh) and committed under profiles/; null when no measurement matches the configuration
         traffic = None
         tpath = os.path.join(ROOT, "profiles", f"gemm_traffic_{a.workload}_b{batch_size}.json")
-        if os.path.exists(tpath):
+        if want_roofline and os.path.exists(tpath):
             with open(tpath) as fh:
                 traffic = int(json.load(fh)["traffic_bytes_per_launch"])  # bytes per launch, like `achieved`
         gflop_pair = M2_TRAIN_GFLOP_PER_PAIR[a.workload] if is_m2 else vtp_train_gflop_per_pair(a.workload, batch_size * world, batch_size)
@@ -579,7 +610,7 @@ def main():
                        # WHICH library served the step (ANTMMF_HIP_LIB can point at another build of the ABI): path relative to the repo, lab or product, size in bytes
                        "library": {"path": os.path.relpath(_lib.lib_path(), os.path.dirname(os.path.abspath(__file__))), "lab": bool(_lib.is_lab()),
                                    "bytes": os.path.getsize(_lib.lib_path()) if os.path.isfile(_lib.lib_path()) else None}},
-            "roofline": {"bound": "mfma", "kernel": "gemm_nt_k64r_kernel / gemm_tn_k64_kernel (bf16 MFMA GEMM family, all layouts)", "achieved": round(achieved, 1),
+            "roofline": None if not want_roofline else {"bound": "mfma", "kernel": "gemm_nt_k64r_kernel / gemm_tn_k64_kernel (bf16 MFMA GEMM family, all layouts)", "achieved": round(achieved, 1),
                          "peak": PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / PEAK_TFLOPS, 4), "traffic": traffic, "traffic_unit": "bytes per launch (L2-miss side: rocprofv3 PMC FETCH_SIZE x2 + WRITE_SIZE, profiles/gemm_traffic_*.json); algorithmic bytes per launch = 2(I R + J R + I J)",
                          "launches_per_step": n // a.steps, "avg_launch_ms": round(gemm_ms / n, 4),
                          "avg_launch_gflop": round(gemm_flops / n / 1e9, 2), "avg_launch_algorithmic_bytes": int(gemm_bytes / n), "gemm_ms_per_step": round(gemm_ms / a.steps, 2),
@@ -587,7 +618,7 @@ def main():
                          # shader clock under the MFMA loop on THIS box (the pool's boxes differ by +-4 % at identical code: compare runs at equal clock)
                          "gemm_clock_mhz": gemm_clock_mhz},
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.workload, a.cpu_sample)
         else:
             out["cpu_baseline"] = None

@@ -747,7 +747,7 @@ def test_m2_step_many_ranks_equals_single_rank(world):
 
 
 @pytest.mark.parametrize("world,outside_gib", [(2, None), (8, 284)])
-def test_bench_two_ranks_dry_run(world, outside_gib):
+def test_bench_two_ranks_dry_run(world, outside_gib, tmp_path):
     """(world 8: the driver's full scaling point; outside_gib: the pretend device reports that much memory OUTSIDE torch's pool -- what RCCL's channel buffers are in
     a real N > 1 run -- so that the probe arithmetic of choose_keep_ffn has to turn the kept-activation policy OFF, on every rank alike.)
     VERDICT r3 item 5(ii): `python bench.py --gpus 2` end to end where there are no GPUs -- bench.py's dry-run mode (host, gloo, lane-emulated kernels, a toy M2)
@@ -767,7 +767,7 @@ def test_bench_two_ranks_dry_run(world, outside_gib):
         env["ANTMMF_BENCH_DRY_OUTSIDE_GIB"] = str(outside_gib)
     env["OMP_NUM_THREADS"] = "1"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "1", "--warmup", "0", "--workload", "tiny", "--batch", "2",
-                          "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=2400)
+                          "--no-cpu-baseline", "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=2400)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -781,6 +781,14 @@ def test_bench_two_ranks_dry_run(world, outside_gib):
     log = j["config"]["grad_buckets"]                                                       # the step's bucket launch order made it into the line
     assert log and sorted(e["bucket"] for e in log) == list(range(len(log))) and all(e["when"] in ("bwd", "end") for e in log)
     assert j["config"]["loss"] == j["config"]["loss"] and j["value"] > 0
+    # --dump-outputs: rank 0's last step as float32 .npy (the loss it returned, its meters, a seeded sample of the updated arena)
+    import numpy as np
+
+    dumped = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert {"loss", "meter_itc_loss", "master_weights_sample", "adam_exp_avg_sample"} <= set(dumped), sorted(dumped)
+    assert all(v.dtype == np.float32 for v in dumped.values())
+    assert abs(float(dumped["loss"]) - j["config"]["loss"]) <= 1e-5 * max(1.0, abs(j["config"]["loss"]))
+    assert dumped["master_weights_sample"].shape == dumped["adam_exp_avg_sample"].shape and np.isfinite(dumped["master_weights_sample"]).all()
 
 
 def test_bench_self_launches_n_ranks(monkeypatch):
