@@ -295,7 +295,7 @@ class _Attention(torch.autograd.Function):
 
 
 def attention(q, k, v, heads, scale, key_bias=None):
-    """softmax(scale q k^T + key_bias) v on [B, N, heads*64] bf16 tensors (views of a packed projection are fine)."""
+    """softmax(scale q k^T + key_bias) v on [B, N, heads*dh] bf16 tensors, head size dh = 64 or 128 (views of a packed projection are fine)."""
     return _Attention.apply(q, k, v, key_bias, heads, scale)
 
 
@@ -453,7 +453,7 @@ class _TransformerLayer(torch.autograd.Function):
             x2 = x2.contiguous()
         T = B * N
         dev = x.device
-        scale = 64 ** -0.5
+        scale = (d // spec.heads) ** -0.5   # head size 64 or 128 (ops._head_dim)
         wqkv, bqkv = _packed_qkv_weight(P, spec)
         pre_ln = spec.kind in ("clip", "m2")
         st1 = None
@@ -547,7 +547,7 @@ class _TransformerLayer(torch.autograd.Function):
         P = dict(zip(SLOTS, params))
         sink = GradSink()
         pre_ln = spec.kind in ("clip", "m2")
-        scale = 64 ** -0.5
+        scale = (d // spec.heads) ** -0.5   # head size 64 or 128 (ops._head_dim)
         p_att, p_hid, seed = ctx.drop
         dy2 = dy.reshape(T, d)
         if not dy2.is_contiguous():

@@ -90,7 +90,7 @@ def layernorm_bwd(dy, x, mean, rstd, gamma, dgamma=None, dbeta=None, dres=None, 
     if dgamma is not None or dbeta is not None or dxsum is not None:  # per-workgroup column-sum partials (the library falls back to atomics without it)
         scratch = _LN_SCRATCH.get(x.device)
         if scratch is None or scratch.numel() < 1024 * 3 * cols:
-            scratch = torch.empty(1024 * 3 * 4096, dtype=torch.float32, device=x.device)
+            scratch = torch.empty(1024 * 3 * max(cols, 4096), dtype=torch.float32, device=x.device)
             _LN_SCRATCH[x.device] = scratch
     _rc(_lib.load().antmmf_act_layernorm_bwd(_p(dy), _p(x), _p(mean), _p(rstd), _p(gamma), _p(dres), _p(dx), _p(dgamma),
                                              _p(dbeta), _p(dxsum), rows, cols, ACT_IDS[act], _dt(x), _p(scratch),

@@ -13,6 +13,7 @@
 // HBM-bound.  Rows up to 1024 columns: one wave (64 lanes) owns a row, the row lives in registers (16-B loads), two-pass
 // mean / centred variance in fp32, wave butterflies only.  Wider rows (the 4d-wide sub-LN): one 256-thread workgroup
 // owns a row (<= 16 elements per thread keeps the register count low and the occupancy up), cross-wave sums through LDS.
+// Rows of 4096 < cols <= 16384 (bf16 only): a 1024- / 512-thread workgroup per row, ln_wide_fwd_kernel / ln_wide_bwd_kernel.
 // Algorithmic bytes / row: fwd 2*cols*sizeof(T) (+8 B stats); bwd 3*cols*sizeof(T) (+ optional residual-gradient read).
 #include "common.h"
 #include <cstdlib>
@@ -357,6 +358,223 @@ __global__ __launch_bounds__(256) void ln_partials_reduce_kernel(const float* __
     }
 }
 
+// ------------------------------------------------------------------ rows wider than 4096 columns (4096 < cols <= 16384, bf16 only)
+// The M2 10B model's ffn_layernorm over the 16384-wide FFN hidden state.  One workgroup per row, thread t owns vectors t + THREADS * i
+// (forward 1024 threads x 2 vectors = 16 columns, backward 512 x 4 = 32), so the row lives in registers.  The forms above do not stretch this far: the wave-per-row backward's [ns][cols] LDS
+// column sums would be 128 - 192 KiB (160 KiB per CU), and the 4096-wide wave-per-row forward already holds 8 vectors per lane at 204 VGPRs.
+// One kernel per direction, everything else (act, dres, dxsum, stats, partials, the re-emitted y) a run-time flag: the product library's
+// kernel budget.  fp32 rows of this width are not served (EINVAL).
+constexpr int LNW_THREADS = 1024, LNW_VPL = 2;              // forward
+constexpr int LNWB_THREADS = 512, LNWB_VPL = 4;             // backward (1024 threads x 2 vectors: 128 VGPRs, the cap, and 104 B of spills)
+
+// sum over an NW-wave workgroup of one / two values; LDS slot `ph` alternates as in row_sum (one barrier per reduction)
+template <int NW>
+__device__ __forceinline__ void lnw_sum2(float& a, float& b, float (*sh)[2 * NW], int& ph) {
+    a = wave_sum(a); b = wave_sum(b);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float* s = sh[ph];
+    ph ^= 1;
+    if (lane == 0) { s[wave] = a; s[NW + wave] = b; }
+    __syncthreads();
+    float ra = 0.f, rb = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) { ra += s[w]; rb += s[NW + w]; }
+    a = ra; b = rb;
+}
+
+__device__ __forceinline__ void lnw_act(f2_t x, int act, f2_t& z, f2_t& dz) {
+    if (act == ANTMMF_ACT_NONE) { z = x; dz = f2_splat(1.0f); }
+    else act_fwd_grad2<-1>(x, act, z, dz);
+}
+
+// Not persistent: grid = rows (the hardware's workgroup turnover, as for the forms above).  64 VGPRs: two workgroups per CU.
+template <typename T>
+__global__ __launch_bounds__(LNW_THREADS) void ln_wide_fwd_kernel(const T* __restrict__ x, const float* __restrict__ gamma,
+                                                                  const float* __restrict__ beta, T* __restrict__ y,
+                                                                  float* __restrict__ mean_out, float* __restrict__ rstd_out,
+                                                                  long rows, int cols, float eps, int act) {
+    __shared__ float sh[2][2 * (LNW_THREADS / 64)];
+    int ph = 0;
+    const int nvec = cols >> 3;
+    const float inv_n = 1.0f / (float)cols;
+    for (long row = blockIdx.x; row < rows; row += gridDim.x) {
+        raw8<T> r[LNW_VPL];
+#pragma unroll
+        for (int i = 0; i < LNW_VPL; ++i) {
+            const int vi = threadIdx.x + LNW_THREADS * i;
+            if (vi < nvec) r[i].load(x + row * cols + vi * 8);
+        }
+        f2_t v[LNW_VPL][4];
+        f2_t s2 = f2_splat(0.f);
+#pragma unroll
+        for (int i = 0; i < LNW_VPL; ++i) {
+            if ((int)threadIdx.x + LNW_THREADS * i < nvec) {
+                r[i].unpack(v[i]);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { f2_t dz_unused; lnw_act(v[i][e], act, v[i][e], dz_unused); s2 += v[i][e]; }
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[i][e] = f2_splat(0.f);
+            }
+        }
+        float sum = s2.x + s2.y, unused = 0.f;
+        lnw_sum2<LNW_THREADS / 64>(sum, unused, sh, ph);
+        const float mean = sum * inv_n;
+        f2_t q2 = f2_splat(0.f);
+#pragma unroll
+        for (int i = 0; i < LNW_VPL; ++i) {
+            if ((int)threadIdx.x + LNW_THREADS * i < nvec) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { v[i][e] = v[i][e] - mean; q2 += v[i][e] * v[i][e]; }   // centred from here on
+            }
+        }
+        float sq = q2.x + q2.y;
+        lnw_sum2<LNW_THREADS / 64>(sq, unused, sh, ph);
+        const float rstd = rsqrtf(sq * inv_n + eps);
+        T* yr = y + row * cols;
+#pragma unroll
+        for (int i = 0; i < LNW_VPL; ++i) {
+            const int vi = threadIdx.x + LNW_THREADS * i;
+            if (vi < nvec) {
+                f2_t g[4], b[4], o[4];
+                ld8_f2<float>(gamma + vi * 8, g);
+                ld8_f2<float>(beta + vi * 8, b);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] = v[i][e] * rstd * g[e] + b[e];
+                st8_f2<T>(yr + vi * 8, o);
+            }
+        }
+        if (threadIdx.x == 0) {
+            if (mean_out) mean_out[row] = mean;
+            if (rstd_out) rstd_out[row] = rstd;
+        }
+    }
+}
+
+// Backward: persistent over rows (grid <= 1024 and <= what is resident), the next row's x / dy in flight while the current one is reduced.
+// Only the RAW bf16 x / dy of the current row stay live across the row reduction; act(x), act'(x) and zhat are rebuilt from them in the
+// second pass (the register room goes to the three column-sum sets).  Each thread accumulates its own columns' dgamma / dbeta (/ dxsum)
+// over its workgroup's rows and writes them once: into the [grid][ns][cols] partials slab (ln_partials_reduce_kernel), or atomics without it.
+// yout (antmmf_layernorm_bwd_renorm): y = zhat * gamma + beta is written too, in the forward kernel's arithmetic (bit-identical y).
+// 512 threads x 4 vectors, 240 VGPRs, no scratch: one workgroup (8 waves) per CU.
+template <typename T>
+__global__ __launch_bounds__(LNWB_THREADS) void ln_wide_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
+                                                                  const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
+                                                                  const float* __restrict__ gamma, const T* __restrict__ dres,
+                                                                  T* __restrict__ dx, float* __restrict__ dgamma,
+                                                                  float* __restrict__ dbeta, float* __restrict__ dxsum, long rows, int cols, int act,
+                                                                  float* __restrict__ partials, const float* __restrict__ beta, T* __restrict__ yout) {
+    ANTMMF_DYN_LDS(float, gb);   // [cols] gamma (+ [cols] beta with yout)
+    __shared__ float sh[2][2 * (LNWB_THREADS / 64)];
+    int ph = 0;
+    const int nvec = cols >> 3;
+    const float inv_n = 1.0f / (float)cols;
+    for (int i = threadIdx.x; i < cols; i += LNWB_THREADS) {
+        gb[i] = gamma[i];
+        if (yout) gb[cols + i] = beta[i];
+    }
+    __syncthreads();
+    f2_t ag[LNWB_VPL][4], ab[LNWB_VPL][4], ad[LNWB_VPL][4];
+#pragma unroll
+    for (int i = 0; i < LNWB_VPL; ++i) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { ag[i][e] = f2_splat(0.f); ab[i][e] = f2_splat(0.f); ad[i][e] = f2_splat(0.f); }
+    }
+    long row = blockIdx.x;
+    const long rstep = gridDim.x;
+    raw8<T> nx[LNWB_VPL], nd[LNWB_VPL];
+    float nmean = 0.f, nrstd = 0.f;
+    auto fetch = [&](long r) {
+#pragma unroll
+        for (int i = 0; i < LNWB_VPL; ++i) {
+            const int vi = threadIdx.x + LNWB_THREADS * i;
+            if (vi < nvec) { nx[i].load(x + r * cols + vi * 8); nd[i].load(dy + r * cols + vi * 8); }
+        }
+        nmean = mean_in[r]; nrstd = rstd_in[r];
+    };
+    if (row < rows) fetch(row);
+    for (; row < rows; row += rstep) {
+        const float mean = nmean, rstd = nrstd;
+        raw8<T> cx[LNWB_VPL], cd[LNWB_VPL], cr[LNWB_VPL];
+#pragma unroll
+        for (int i = 0; i < LNWB_VPL; ++i) { cx[i] = nx[i]; cd[i] = nd[i]; }
+        if (row + rstep < rows) fetch(row + rstep);
+        if (dres) {   // this row's residual gradient: in flight during the first pass and the row reduction
+#pragma unroll
+            for (int i = 0; i < LNWB_VPL; ++i) {
+                const int vi = threadIdx.x + LNWB_THREADS * i;
+                if (vi < nvec) cr[i].load(dres + row * cols + vi * 8);
+            }
+        }
+        f2_t s1v = f2_splat(0.f), s2v = f2_splat(0.f);
+#pragma unroll
+        for (int i = 0; i < LNWB_VPL; ++i) {
+            const int vi = threadIdx.x + LNWB_THREADS * i;
+            if (vi < nvec) {
+                f2_t xv[4], dv[4], gm[4], yv[4];
+                cx[i].unpack(xv); cd[i].unpack(dv);
+                ld8_f2<float>(gb + vi * 8, gm);
+                if (yout) ld8_f2<float>(gb + cols + vi * 8, yv);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    f2_t z, da_unused;
+                    lnw_act(xv[e], act, z, da_unused);
+                    const f2_t zh = (z - mean) * rstd;
+                    if (yout) yv[e] = zh * gm[e] + yv[e];
+                    const f2_t ge = dv[e] * gm[e];
+                    s1v += ge;
+                    s2v += ge * zh;
+                    ag[i][e] += dv[e] * zh;
+                    ab[i][e] += dv[e];
+                }
+                if (yout) st8_f2<T>(yout + row * cols + vi * 8, yv);
+            }
+        }
+        float c1 = s1v.x + s1v.y, c2 = s2v.x + s2v.y;
+        lnw_sum2<LNWB_THREADS / 64>(c1, c2, sh, ph);
+        c1 *= inv_n; c2 *= inv_n;
+#pragma unroll
+        for (int i = 0; i < LNWB_VPL; ++i) {
+            const int vi = threadIdx.x + LNWB_THREADS * i;
+            if (vi < nvec) {
+                f2_t xv[4], dv[4], gm[4], rs[4], o[4];
+                if (dres) cr[i].unpack(rs);
+                cx[i].unpack(xv); cd[i].unpack(dv);
+                ld8_f2<float>(gb + vi * 8, gm);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    f2_t z, da;
+                    lnw_act(xv[e], act, z, da);
+                    const f2_t zh = (z - mean) * rstd;
+                    o[e] = rstd * (dv[e] * gm[e] - c1 - zh * c2);
+                    if (act != ANTMMF_ACT_NONE) o[e] *= da;
+                    if (dres) o[e] += rs[e];
+                    if (dxsum) ad[i][e] += o[e];
+                }
+                st8_f2<T>(dx + row * cols + vi * 8, o);
+            }
+        }
+    }
+    const int ns = dxsum ? 3 : 2;
+#pragma unroll
+    for (int i = 0; i < LNWB_VPL; ++i) {
+        const int vi = threadIdx.x + LNWB_THREADS * i;
+        if (vi >= nvec) continue;
+        if (partials) {   // per-workgroup partial column sums [grid][ns][cols]
+            float* pg = partials + (long)blockIdx.x * ns * cols;
+            st8_f2<float>(pg + vi * 8, ag[i]); st8_f2<float>(pg + cols + vi * 8, ab[i]);
+            if (dxsum) st8_f2<float>(pg + 2 * cols + vi * 8, ad[i]);
+        } else {           // a thread owns its columns within the workgroup: straight to global
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                if (dgamma) atomicAdd(&dgamma[vi * 8 + e], ag[i][e >> 1][e & 1]);
+                if (dbeta) atomicAdd(&dbeta[vi * 8 + e], ab[i][e >> 1][e & 1]);
+                if (dxsum) atomicAdd(&dxsum[vi * 8 + e], ad[i][e >> 1][e & 1]);
+            }
+        }
+    }
+}
+
 #define LN_FWD_ROWS_PER_WAVE 1   /* product default of the wave-per-row forward forms (see ln_fwd_launch) */
 template <typename T>
 static int ln_fwd_launch(const void* x, const float* g, const float* b, void* y, float* mean, float* rstd, long rows,
@@ -387,7 +605,10 @@ static int ln_fwd_launch(const void* x, const float* g, const float* b, void* y,
         // insensitive to an occupancy limiter); fp32 rows would need > 256 VGPRs and keep the workgroup form
         if (sizeof(T) == 2 && nvec > 256) LN_FWD(8, false, gw); else LN_FWD(2, true, gb);
     }
-    else return ANTMMF_EINVAL;
+    else if constexpr (sizeof(T) == 2) {   // 4096 < cols <= 16384 (ln_args_ok): bf16 only
+        hipLaunchKernelGGL((ln_wide_fwd_kernel<T>), dim3(gb), dim3(LNW_THREADS), 0, s, (const T*)x, g, b, (T*)y, mean, rstd, rows, cols, eps, act);
+    }
+    else return ANTMMF_EINVAL;   // fp32 rows wider than 4096: not served
 #undef LN_FWD
 #undef LN_FWD_A
     return antmmf_check_launch();
@@ -397,13 +618,13 @@ static int ln_fwd_launch(const void* x, const float* g, const float* b, void* y,
 // 256-thread workgroups fit a CU -- 768 resident, the last 256 ran as a second, one-third-full round (round 3: 1.446 -> 1.339 ms on 263168 x 4096, 0.468 -> 0.439 ms on
 // 78848 rows with a 768-workgroup grid; 512 and 1536 are both slower).  Asked from the runtime per kernel variant (they differ in registers), capped by `cap`.
 template <typename K>
-static int ln_resident_grid(K kern, size_t lds, int cap) {
+static int ln_resident_grid(K kern, size_t lds, int cap, int threads = 256) {
 #ifdef ANTMMF_EMULATE
-    (void)kern; (void)lds;
+    (void)kern; (void)lds; (void)threads;
     return cap;
 #else
     int per_cu = 0, dev = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, lds) != hipSuccess || per_cu <= 0) return cap;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds) != hipSuccess || per_cu <= 0) return cap;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return cap;
     const long g = (long)per_cu * cus;
     return (int)(g < cap ? g : cap);
@@ -446,7 +667,17 @@ static int ln_bwd_launch(const void* dy, const void* x, const float* mean, const
     else if (nvec <= 128) LN_BWD(2, false, gw, lds);
     else if (nvec <= 256) LN_BWD(1, true, gb, ldsb);
     else if (nvec <= 512) LN_BWD(2, true, gb, ldsb);
-    else return ANTMMF_EINVAL;
+    else if constexpr (sizeof(T) == 2) {   // 4096 < cols <= 16384 (ln_args_ok): bf16 only, one kernel for every option
+        static int res = 0;   // resident 512-thread workgroups (LDS: gamma, and beta with yout; <= 128 KiB, above the 64-KiB default)
+        if (!res) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ln_wide_bwd_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 16384 * (int)sizeof(float));
+            res = ln_resident_grid(ln_wide_bwd_kernel<T>, (size_t)2 * 16384 * sizeof(float), 1024, LNWB_THREADS);
+        }
+        gb_used = gb < res ? gb : res;
+        hipLaunchKernelGGL((ln_wide_bwd_kernel<T>), dim3(gb_used), dim3(LNWB_THREADS), ldsb, s, (const T*)dy, (const T*)x, mean, rstd, g, (const T*)dres, (T*)dx,
+                           dgamma, dbeta, dxsum, rows, cols, act, partials, beta, (T*)yout);
+    }
+    else return ANTMMF_EINVAL;   // fp32 rows wider than 4096: not served
 #undef LN_BWD
 #undef LN_BWD_A
 #undef LN_BWD_D
@@ -457,7 +688,7 @@ static int ln_bwd_launch(const void* dy, const void* x, const float* mean, const
     return antmmf_check_launch();
 }
 
-static int ln_args_ok(long rows, int cols) { return rows >= 0 && cols > 0 && !(cols & 7) && cols <= 4096; }
+static int ln_args_ok(long rows, int cols) { return rows >= 0 && cols > 0 && !(cols & 7) && cols <= 16384; }
 
 extern "C" int antmmf_act_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
                                         long rows, int cols, float eps, int act, int dtype, hipStream_t stream) {

@@ -13,8 +13,8 @@ class MultiheadAttention(nn.Module):
         assert self_attention and not encoder_decoder_attention
         self.embed_dim, self.num_heads = embed_dim, num_heads
         self.head_dim = embed_dim // num_heads
-        if self.head_dim != 64:
-            raise ValueError("the fused attention kernel is specialised for head_dim 64 (all M2 sizes)")
+        if embed_dim % num_heads or self.head_dim not in (64, 128):
+            raise ValueError(f"head_dim {embed_dim}/{num_heads}: the HIP attention kernels serve head sizes 64 (M2 base / large) and 128 (M2 huge, Encoder_10B)")
         self.scaling = self.head_dim ** -0.5
         self.k_proj = MultiwayWrapper(args, nn.Linear(embed_dim, embed_dim, bias=True))
         self.v_proj = MultiwayWrapper(args, nn.Linear(embed_dim, embed_dim, bias=True))

@@ -52,7 +52,8 @@ int antmmf_abi_version(void);
 /* ---- LayerNorm: y = (x - mean) * rstd * gamma + beta, statistics in fp32.
  * Replaces clip/model.py:213-219 (fp32-upcast LN), modeling_bert.py:63 (eps 1e-12),
  * torchscale LayerNorm (encoder.py:34,77; multihead_attention.py:51-55; feedforward_network.py:109).
- * cols % 8 == 0, cols <= 4096.  mean/rstd ([rows] fp32) may be NULL in fwd. */
+ * cols % 8 == 0; cols <= 4096 for fp32, cols <= 16384 for bf16 (4096 < cols: the M2 10B model's 16384-wide ffn_layernorm; fp32 rows
+ * that wide return ANTMMF_EINVAL).  The same limits hold for every LayerNorm entry point below.  mean/rstd ([rows] fp32) may be NULL in fwd. */
 int antmmf_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
                          int64_t rows, int cols, float eps, int dtype, antmmf_stream_t stream);
 /* dx = LN'(dy) (+ dres if non-NULL); dgamma/dbeta (fp32, may be NULL) are ACCUMULATED (+=). */
