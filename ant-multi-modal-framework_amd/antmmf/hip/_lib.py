@@ -55,6 +55,12 @@ _SIGNATURES = {
     "antmmf_gemm_bf16_gated_colsum_ok": [I, I, I, L, L],
     "antmmf_gemm_bf16_gated_colsum": [P, P, P, I, I, I, L, L, L, P, L, P, P],
     "antmmf_attention_bwd_sums_ok": [I, I, I, F],
+    "antmmf_attention_packed_ok": [I, I],
+    "antmmf_attention_fwd_packed": [P, P, P, P, P, P, I, I, I, L, L, L, L, F, P],
+    "antmmf_attention_bwd_packed": [P, P, P, P, P, P, P, P, P, P, I, I, I, L, L, L, L, L, L, L, L, F, P],
+    "antmmf_attention_bwd_sums_packed": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, L, L, L, L, L, L, L, L, F, P],
+    "antmmf_embed_gather_packed": [P, P, P, P, P, P, L, I, I, I, P],
+    "antmmf_embed_scatter_add_pos_packed": [P, P, P, L, I, I, I, P],
     "antmmf_attention_bwd_sums": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, L, L, L, L, L, L, L, L, F, P],
     "antmmf_milnce_fwd": [P, P, I, I, I, I, I, P, P, P],
     "antmmf_milnce_bwd": [P, P, P, P, I, I, I, I, I, P, P, I, P],

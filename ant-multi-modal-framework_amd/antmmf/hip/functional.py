@@ -443,11 +443,17 @@ def _folded_w2(P):
 
 class _TransformerLayer(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, key_bias, spec, seed, *params):
+    def forward(ctx, x, key_bias, spec, seed, text, *params):
         P = dict(zip(SLOTS, params))
         p_att, p_hid = (spec.attn_dropout, spec.hidden_dropout) if spec.kind == "bert" else (0.0, 0.0)
         seed = int(seed or 0)
-        B, N, d = x.shape
+        if text is not None:
+            # token-packed input [T, d] (PackedText): every row kernel and GEMM below sees T rows instead of B * n_max; only the attention calls know about items
+            if x.dim() != 2 or x.shape[0] != text.rows or key_bias is not None or p_att > 0 or KEY_IMPORTANCE is not None:
+                raise ValueError("transformer_layer: a packed input is [rows, d] with its PackedText table, no key_bias, no attention dropout, no key-importance collector")
+            B, N, d = 1, x.shape[0], x.shape[1]
+        else:
+            B, N, d = x.shape
         x2 = x.reshape(B * N, d)
         if not x2.is_contiguous():
             x2 = x2.contiguous()
@@ -465,7 +471,13 @@ class _TransformerLayer(torch.autograd.Function):
         qkv = ops.gemm(h, wqkv, bias=bqkv)  # [T, 3d]
         del h
         q3 = qkv.view(B, N, 3 * d)
-        o, lse = ops.attention_fwd(q3[..., :d], q3[..., d:2 * d], q3[..., 2 * d:], spec.heads, scale, key_bias, p_att, seed)
+        if text is not None:
+            o = torch.empty(T, d, dtype=BF, device=dev)
+            if T > text.total:
+                o[text.total:].zero_()   # the tail rows belong to no item: the kernel leaves them alone, and everything downstream must stay finite (their gradients are exact zeros)
+            o, lse = ops.attention_fwd_packed(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], text.items, spec.heads, scale, text.n_max, o=o)
+        else:
+            o, lse = ops.attention_fwd(q3[..., :d], q3[..., d:2 * d], q3[..., 2 * d:], spec.heads, scale, key_bias, p_att, seed)
         if KEY_IMPORTANCE is not None:   # `output_attentions=True` callers: the head-mean column sums of this layer's probabilities join the collector
             ops.attention_key_importance_(KEY_IMPORTANCE, q3[..., :d], q3[..., d:2 * d], lse, spec.heads, scale, key_bias, p_att, seed or 0, weight=1.0 / spec.heads)
         o2 = o.view(T, d)
@@ -525,13 +537,14 @@ class _TransformerLayer(torch.autograd.Function):
             saved += list(st) if st is not None else [None, None]
         saved.append(s2)
         saved.append(kept_gn)
-        y3 = y.view(B, N, d)
+        y3 = y.view(B, N, d) if text is None else y
         saved.append(y3 if fold else None)   # the fold's backward takes one of the LayerNorm's row means from the layer output (an output may be saved)
         saved.append(h2 if (KEEP_LN2_OUT and pre_ln) else None)
         ctx.save_for_backward(*saved, *params)
         ctx.spec, ctx.shape, ctx.nsaved, ctx.drop = spec, (B, N, d), len(saved), (p_att, p_hid, seed)
         ctx.u_is_grad = bool(KEEP_FFN_NORM and spec.kind != "m2")
         ctx.fold = fold
+        ctx.text = text
         return y3
 
     @staticmethod
@@ -673,18 +686,27 @@ class _TransformerLayer(torch.autograd.Function):
         if not bo_fused:
             _bgrad(sink, P["bo"], dy_wo)
         del o_n
+        text = ctx.text
         q3 = qkv.view(B, N, 3 * d)
         dqkv = torch.empty(B, N, 3 * d, dtype=BF, device=qkv.device)
+        n_items, n_tok = (B, N) if text is None else (text.items.shape[0], text.n_max)
         # q / k / v bias gradients: the one-kernel attention backward also returns, per batch item, the token sums of dQ | dK | dV ([B, 3d] fp32) -- their column
         # sums are the bias gradients, so the column-sum passes over the B * N rows of dQ | dK | dV (0.19 ms per image-tower layer of the flagship) are not run
         qkv_biases = [P["bqkv"]] if spec.packed_qkv else [P["bq"], P["bk"], P["bv"]]
         tok_sums = None
         # (ATTN_BWD_SUMS_MIN_TOKENS = 129 restricts it to the long towers: the A/B of profiles/r6b_attn_bwd_token_sums_ab.txt -- the short towers gain too, a little)
-        if (ATTN_BWD_SUMS and N >= ATTN_BWD_SUMS_MIN_TOKENS and d == 64 * spec.heads and any(b_ is not None and b_.requires_grad for b_ in qkv_biases)
-                and ops.attention_bwd_sums_ok(64, N, N, p_att)):
-            tok_sums = torch.empty(B, 3 * d, dtype=torch.float32, device=qkv.device)
-        ops.attention_bwd(q3[..., :d], q3[..., d:2 * d], q3[..., 2 * d:], o, lse, do.view(B, N, d), spec.heads, scale, key_bias,
-                          dq=dqkv[..., :d], dk=dqkv[..., d:2 * d], dv=dqkv[..., 2 * d:], dropout_p=p_att, dropout_seed=seed, sums=tok_sums, sums_v=not bv_fused)
+        if (ATTN_BWD_SUMS and n_tok >= ATTN_BWD_SUMS_MIN_TOKENS and d == 64 * spec.heads and any(b_ is not None and b_.requires_grad for b_ in qkv_biases)
+                and ops.attention_bwd_sums_ok(64, n_tok, n_tok, p_att)):
+            tok_sums = torch.empty(n_items, 3 * d, dtype=torch.float32, device=qkv.device)
+        if text is not None:
+            dq2 = dqkv.view(T, 3 * d)
+            if T > text.total:
+                dq2[text.total:].zero_()   # rows of no item: not written by the kernel, read by the wgrads and the dgrad below
+            ops.attention_bwd_packed(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], text.items, o, lse, do, spec.heads, scale, text.n_max,
+                                     dq2[:, :d], dq2[:, d:2 * d], dq2[:, 2 * d:], sums=tok_sums, sums_v=not bv_fused)
+        else:
+            ops.attention_bwd(q3[..., :d], q3[..., d:2 * d], q3[..., 2 * d:], o, lse, do.view(B, N, d), spec.heads, scale, key_bias,
+                              dq=dqkv[..., :d], dk=dqkv[..., d:2 * d], dv=dqkv[..., 2 * d:], dropout_p=p_att, dropout_seed=seed, sums=tok_sums, sums_v=not bv_fused)
         del do
         dqkv2 = dqkv.view(T, 3 * d)
         bsrc = tok_sums if tok_sums is not None else dqkv2   # what the q / k / v bias gradients are column sums of
@@ -734,29 +756,30 @@ class _TransformerLayer(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             if not pre_ln:
                 dx = ops.gemm(dqkv2, _packed_qkv_weight_t(P, spec), residual=dmid)
-            dx = dx.view(B, N, d)
+            dx = dx.view(B, N, d) if text is None else dx.view(T, d)
             if pre_ln:
                 # for the previous layer's fc2 bias gradient (see above): valid only for this very tensor, unmodified
                 dx._antmmf_colsum = (dx_colsum, dx._version, dx.data_ptr(), tuple(dx.shape))
         else:
             dx = None
-        grads = [sink.result(p, p is not None and ctx.needs_input_grad[4 + i]) for i, p in enumerate(params)]
+        grads = [sink.result(p, p is not None and ctx.needs_input_grad[5 + i]) for i, p in enumerate(params)]
         arena = next((getattr(p, "_antmmf_arena", None) for p in params if p is not None), None)
         if arena is not None:
             arena.note_backward(params)   # these parameters' gradients may now be final: their bucket's all-reduce can start
-        return (dx, None, None, None, *grads)
+        return (dx, None, None, None, None, *grads)
 
 
-def transformer_layer(x, spec, params, key_bias=None, seed=None):
+def transformer_layer(x, spec, params, key_bias=None, seed=None, packed=None):
     """x [B, N, d] bf16 -> [B, N, d]; `params` maps SLOTS names to fp32 master parameters.  `seed`: dropout seed of this call
-    (BERT layers with dropout > 0 only); None draws one from torch's CPU generator (host side: no device sync)."""
+    (BERT layers with dropout > 0 only); None draws one from torch's CPU generator (host side: no device sync).
+    `packed` (a PackedText): x is the token-packed [rows, d] matrix of a ragged batch -- no padding rows are computed -- and so is the result."""
     if seed is None and spec.kind == "bert" and (spec.attn_dropout > 0 or spec.hidden_dropout > 0):
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())
     plist = [params.get(s) for s in SLOTS]
     arena = next((getattr(p, "_antmmf_arena", None) for p in plist if p is not None), None)
     if arena is not None and torch.is_grad_enabled():
         arena.note_forward(plist)   # gradient all-reduce under the backward pass (arena.arm_overlap): counts this use of the parameters
-    return _TransformerLayer.apply(x, key_bias, spec, seed, *plist)
+    return _TransformerLayer.apply(x, key_bias, spec, seed, packed, *plist)
 
 
 # ------------------------------------------------------------------------------ embeddings
@@ -853,3 +876,135 @@ def embed(ids, word, pos=None, type_table=None, zero_rows=None, pos_offset=0, pa
     """padding_idx: table row that receives no gradient (torch.nn.Embedding's padding_idx)."""
     _note_untracked(word, pos, type_table)
     return _Embed.apply(ids, word, pos, type_table, zero_rows, pos_offset, padding_idx)
+
+
+# ------------------------------------------------------------------------------ token-packed text batches
+# A ragged text batch as ONE [rows, d] matrix of real tokens, item after item (M2 text tower: captions of 8 ... 77 tokens padded to 77 are 45 % padding, and every GEMM,
+# LayerNorm and attention launch of the tower ran on it).  PACK_TEXT is the module flag of the A/B and of the parity tests (False: the padded path everywhere).
+PACK_TEXT = True
+PACK_ROW_MULTIPLE = 2048   # rows are rounded up so that the caching allocator sees a handful of sizes (sum of lengths at 1024 captions: sigma ~ 650 rows)
+PACK_ROW_MULTIPLE_SMALL = 64
+
+
+class PackedText:
+    """items: int32 [B, 2] device table (first row, length); n_max: the longest allowed item (the padded width); total: sum of the lengths (host int);
+    rows: row count of the packed matrices, >= total -- the rows behind `total` belong to no item and hold zeros."""
+
+    def __init__(self, items, n_max, total, rows):
+        self.items, self.n_max, self.total, self.rows = items, int(n_max), int(total), int(rows)
+        self._row0 = None
+        self._valid = None
+
+    @property
+    def row0(self):
+        """int64 [B]: the row of every item's first token (CLS)"""
+        if self._row0 is None:
+            self._row0 = self.items[:, 0].long()
+        return self._row0
+
+    @property
+    def valid(self):
+        """bool [B, n_max]: token n of item b exists"""
+        if self._valid is None:
+            self._valid = torch.arange(self.n_max, device=self.items.device)[None, :] < self.items[:, 1:2]
+        return self._valid
+
+    def unpack(self, x):
+        """packed [rows, d] -> padded [B, n_max, d] with zero rows behind every item's length (differentiable; for callers that want per-token features)"""
+        idx = (self.row0[:, None] + torch.arange(self.n_max, device=x.device)[None, :]).clamp_(max=self.rows - 1)
+        out = x.index_select(0, idx.reshape(-1)).view(idx.shape[0], self.n_max, x.shape[-1])
+        return out * self.valid[..., None].to(out.dtype)
+
+
+class PackedTextPlan:
+    """What packed_text_begin enqueued: the device item table plus a tiny device-to-host copy of (sum of lengths, mask-is-a-prefix-mask) on a side stream."""
+
+    def __init__(self, mask, items, info_dev, info_host, event):
+        self.mask, self.items, self.info_dev, self.info_host, self.event = mask, items, info_dev, info_host, event
+
+
+_SIDE_STREAMS = {}
+
+
+def packed_text_begin(mask, head_dim=64):
+    """mask [B, N] (non-zero = token).  Enqueues, on the current stream, the length reduction, the prefix check (real tokens first, at least one per item) and the item
+    table, and on a SIDE stream the copy of the two integers the host needs (the row count sizes every launch of the tower).  Call it before other work is enqueued --
+    compute_itc does, ahead of the image tower -- so that packed_text_finish waits for that copy only, never for the compute stream.  None: this batch is not packed
+    (flag off; head size or width not served by the packed attention kernels: 64, 33 ... 128 tokens)."""
+    if not PACK_TEXT or mask is None or mask.dim() != 2 or not ops.attention_packed_ok(head_dim, mask.shape[1]):
+        return None
+    B, N = mask.shape
+    m = mask != 0
+    lengths = m.sum(dim=1)
+    prefix = (m == (torch.arange(N, device=mask.device)[None, :] < lengths[:, None])).all() & (lengths.min() >= 1)
+    ends = torch.cumsum(lengths, 0)
+    items = torch.stack([ends - lengths, lengths], dim=1).to(torch.int32).contiguous()
+    info_dev = torch.stack([ends[-1], prefix.to(ends.dtype)])
+    if mask.is_cuda:
+        cur = torch.cuda.current_stream(mask.device)
+        side = _SIDE_STREAMS.get(mask.device)
+        if side is None:
+            side = _SIDE_STREAMS[mask.device] = torch.cuda.Stream(mask.device)
+        info_host = torch.empty(2, dtype=info_dev.dtype, pin_memory=True)
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            info_host.copy_(info_dev, non_blocking=True)
+            event = torch.cuda.Event()
+            event.record(side)
+        info_dev.record_stream(side)
+        return PackedTextPlan(mask, items, info_dev, info_host, event)
+    return PackedTextPlan(mask, items, info_dev, info_dev, None)
+
+
+def packed_text_finish(plan):
+    """-> PackedText, or None when the batch takes the padded path (no plan; the mask is not a prefix mask)."""
+    if plan is None:
+        return None
+    if plan.event is not None:
+        plan.event.synchronize()   # the side stream's copy: issued before the image tower, long done when the text tower is reached
+    total, ok = int(plan.info_host[0]), int(plan.info_host[1])
+    if not ok:
+        return None
+    B, N = plan.mask.shape
+    mult = PACK_ROW_MULTIPLE if B * N >= 16 * PACK_ROW_MULTIPLE else PACK_ROW_MULTIPLE_SMALL
+    rows = (total + mult - 1) // mult * mult
+    return PackedText(plan.items, N, total, rows)
+
+
+class _EmbedPacked(torch.autograd.Function):
+    """_Embed (word + position) straight into the packed matrix: row items[b, 0] + n = word[ids[b, n]] + pos[pos_offset + n] for n < items[b, 1]; no padded tensor exists."""
+
+    @staticmethod
+    def forward(ctx, ids, word, pos, text, pos_offset, padding_idx):
+        out = torch.empty(text.rows, word.shape[1], dtype=BF, device=word.device)
+        if text.rows > text.total:
+            out[text.total:].zero_()
+        ops.embed_gather_packed(ids.contiguous(), f32(word), f32(pos), text.items, out, pos_offset)
+        ctx.save_for_backward(ids, word, pos)
+        ctx.text, ctx.pos_offset, ctx.padding_idx = text, pos_offset, padding_idx
+        return out
+
+    @staticmethod
+    def backward(ctx, dx):
+        ids, word, pos = ctx.saved_tensors
+        text = ctx.text
+        dx = dx.contiguous()
+        seq = ids.shape[1]
+        sink = GradSink()
+        if word.requires_grad:
+            # the sorted scatter (one writer per table row) over the PADDED ids -- tokens without a row, and padding_idx, sort behind the table -- reading packed rows
+            keep = text.valid if ctx.padding_idx is None else (text.valid & (ids != ctx.padding_idx))
+            keys = torch.where(keep, ids, torch.full_like(ids, word.shape[0])).reshape(-1)
+            sorted_idx, src = torch.sort(keys, stable=True)
+            packed_row = (text.row0[:, None] + torch.arange(seq, device=ids.device)[None, :]).reshape(-1)
+            ops.embed_scatter_add_sorted_(sink.buf(word), dx, sorted_idx, packed_row[src].contiguous())
+        if pos is not None and pos.requires_grad:
+            ops.embed_scatter_add_pos_packed_(sink.buf(pos), dx, text.items, seq, offset=ctx.pos_offset)
+        ng = ctx.needs_input_grad
+        return (None, sink.result(word, ng[1]), sink.result(pos, pos is not None and ng[2]), None, None, None)
+
+
+def embed_packed(ids, word, pos, text, pos_offset=0, padding_idx=None):
+    """ids [B, n_max] padded as the loader delivers them -> the packed [text.rows, d] bf16 embedding (tail rows zero)."""
+    _note_untracked(word, pos)
+    return _EmbedPacked.apply(ids, word, pos, text, pos_offset, padding_idx)

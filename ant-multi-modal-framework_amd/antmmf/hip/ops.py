@@ -628,6 +628,92 @@ def attention_bwd(q, k, v, o, lse, d_o, heads, scale, key_bias=None, dq=None, dk
     return dq, dk, dv
 
 
+# ------------------------------------------------------------------------------ token-packed self-attention / embedding (the M2 text tower without its padding)
+def _row_ld(t, name):
+    """row stride (elements) of a [T, D] matrix that may be a column slice of a packed projection"""
+    if t.dim() != 2 or t.stride(1) != 1:
+        raise ValueError(f"{name}: expected a [T, D] matrix with unit column stride")
+    return t.stride(0)
+
+
+def _items_ok(items, name="items"):
+    if items.dtype != torch.int32 or items.dim() != 2 or items.shape[1] != 2 or not items.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous int32 [B, 2] table of (first row, length)")
+
+
+def attention_packed_ok(head_dim, n_max):
+    """True when the packed entry points serve items of up to n_max tokens (head size 64, 33 ... 128)."""
+    return bool(_lib.load().antmmf_attention_packed_ok(int(head_dim), int(n_max)))
+
+
+def attention_fwd_packed(q, k, v, items, heads, scale, n_max, o=None):
+    """q | k | v [T, D] (column slices of one packed projection are fine) holding item b's tokens at rows items[b, 0] ... + items[b, 1] - 1.
+    -> o [T, D] (rows of no item are left as they are: pass `o` to choose what they hold), lse [B, heads, n_max]."""
+    _dev_ok(q, k, v, items, o); _items_ok(items)
+    T, D = q.shape
+    B = items.shape[0]
+    if _head_dim(D, heads) != 64:
+        raise ValueError("attention_fwd_packed: head size 64 only")
+    if o is None:
+        o = torch.empty(T, D, dtype=torch.bfloat16, device=q.device)
+    _c(o, "o")
+    lse = torch.empty(B, heads, n_max, dtype=torch.float32, device=q.device)
+    _rc(_lib.load().antmmf_attention_fwd_packed(_p(q), _p(k), _p(v), _p(items), _p(o), _p(lse), B, heads, int(n_max), _row_ld(q, "q"), _row_ld(k, "k"),
+                                                _row_ld(v, "v"), D, float(scale), _stream()), "antmmf_attention_fwd_packed")
+    return o, lse
+
+
+def attention_bwd_packed(q, k, v, items, o, lse, d_o, heads, scale, n_max, dq, dk, dv, sums=None, sums_v=True):
+    """Backward of attention_fwd_packed into dq | dk | dv [T, D] (given: rows of no item are not written); sums [B, 3 * D] fp32 as in attention_bwd."""
+    _dev_ok(q, k, v, items, o, lse, d_o, dq, dk, dv, sums); _items_ok(items)
+    T, D = q.shape
+    B = items.shape[0]
+    _c(o, "o"); _c(d_o, "d_o"); _c(lse, "lse")
+    if _head_dim(D, heads) != 64 or tuple(lse.shape) != (B, heads, n_max):
+        raise ValueError("attention_bwd_packed: head size 64 and lse [B, heads, n_max]")
+    lds = (_row_ld(q, "q"), _row_ld(k, "k"), _row_ld(v, "v"), D, D, _row_ld(dq, "dq"), _row_ld(dk, "dk"), _row_ld(dv, "dv"))
+    if sums is not None:
+        _c(sums, "sums"); _f32(sums, "sums")
+        if tuple(sums.shape) != (B, 3 * D):
+            raise ValueError("attention_bwd_packed: sums must be [B, 3 * D] fp32")
+        _rc(_lib.load().antmmf_attention_bwd_sums_packed(_p(q), _p(k), _p(v), _p(items), _p(o), _p(lse), _p(d_o), _p(dq), _p(dk), _p(dv), _p(sums),
+                                                         1 if sums_v else 0, B, heads, int(n_max), *lds, float(scale), _stream()),
+            "antmmf_attention_bwd_sums_packed")
+    else:
+        _rc(_lib.load().antmmf_attention_bwd_packed(_p(q), _p(k), _p(v), _p(items), _p(o), _p(lse), _p(d_o), _p(dq), _p(dk), _p(dv), B, heads, int(n_max),
+                                                    *lds, float(scale), _stream()), "antmmf_attention_bwd_packed")
+    return dq, dk, dv
+
+
+def embed_gather_packed(ids, word, pos, items, out, pos_offset=0):
+    """Token n < items[b, 1] of ids[b] -> out[items[b, 0] + n] = word[id] + pos[pos_offset + n] (bf16); nothing else of `out` [T, d] is written."""
+    _dev_ok(ids, word, pos, items, out); _c(ids, "ids"); _c(out, "out"); _items_ok(items)
+    assert ids.dtype == torch.int64 and out.dtype == torch.bfloat16
+    b, seq = ids.shape
+    assert items.shape[0] == b and out.shape[1] == word.shape[1]
+    _rc(_lib.load().antmmf_embed_gather_packed(_p(ids), _p(word), _p(pos), None, _p(items), _p(out), b * seq, seq, word.shape[1], pos_offset, _stream()),
+        "antmmf_embed_gather_packed")
+    return out
+
+
+def embed_scatter_add_pos_packed_(dtable, dx, items, seq, offset=0):
+    """dtable[offset + n] += sum over the items longer than n of the packed dx[items[b, 0] + n]"""
+    _dev_ok(dtable, dx, items); _c(dx, "dx"); _f32(dtable, "dtable"); _c(dtable, "dtable"); _items_ok(items)
+    _rc(_lib.load().antmmf_embed_scatter_add_pos_packed(_p(dx), _p(items), _p(dtable), items.shape[0], int(seq), dx.shape[-1], offset, _stream()),
+        "antmmf_embed_scatter_add_pos_packed")
+    return dtable
+
+
+def embed_scatter_add_sorted_(dtable, dx, sorted_idx, src_row):
+    """The sorted word-table scatter with caller-made keys: dtable[sorted_idx[j]] += dx[src_row[j]] (ids >= the table's rows are skipped) -- the packed text
+    tower hands in packed source rows."""
+    _dev_ok(dtable, dx, sorted_idx, src_row); _c(dx, "dx"); _f32(dtable, "dtable"); _c(dtable, "dtable"); _c(sorted_idx, "sorted_idx"); _c(src_row, "src_row")
+    assert sorted_idx.dtype == torch.int64 and src_row.dtype == torch.int64
+    _rc(_lib.load().antmmf_embed_scatter_add_sorted(_p(dx), _p(sorted_idx), _p(src_row), _p(dtable), sorted_idx.numel(), dtable.shape[0], dx.shape[-1], _stream()),
+        "antmmf_embed_scatter_add_sorted")
+    return dtable
+
+
 # ------------------------------------------------------------------------------ losses
 def milnce_fwd(Rm, Cm, n_pair, row_offset):
     _dev_ok(Rm, Cm); _c(Rm, "Rm"); _c(Cm, "Cm"); _f32(Rm, "Rm"); _f32(Cm, "Cm")

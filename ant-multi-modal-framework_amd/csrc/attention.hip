@@ -73,7 +73,27 @@ struct AttnArgs {
     float* sums;
     int fwd_stagger;   // (lab experiment, see attn_fwd_kernel; 0 in the product)
     int sums_v;   // 0: the dV sums are not wanted (their slots stay unwritten) -- torchscale's value bias comes out of the inner LayerNorm's backward
+    // Token-packed self-attention (the *_packed entry points; forward <= 96 keys and the EARLY persistent one-kernel backward only): items[2 b] = first row of batch item b
+    // in the packed q | k | v | o | dO | dq | dk | dv matrices, items[2 b + 1] = its length (1 ... Nq = Nk, the longest ALLOWED item: it sizes the tiles, the launch and
+    // the [B, heads, Nq] layout of lse).  Keys at or beyond the length are masked exactly as a -inf key_bias masks them, queries at or beyond it are neither read (the
+    // fetches clamp to the item's last row) nor stored.  NULL = item b starts at row b * N and has N tokens: the strided addressing of every other entry point.
+    const int* items;
 };
+// first row and token count of batch item b (wave-uniform: b comes from blockIdx / the persistent item counter, so both live in SGPRs)
+struct AttnItem { long q0, k0; int nq, nk; };
+__device__ __forceinline__ AttnItem attn_item(const AttnArgs& a, int b) {
+    AttnItem it;
+    if (a.items) { const int n = a.items[2 * b + 1]; it.q0 = it.k0 = a.items[2 * b]; it.nq = it.nk = n < a.Nq ? n : a.Nq; }   // (a length beyond n_max would index past lse's rows)
+    else { it.q0 = (long)b * a.Nq; it.k0 = (long)b * a.Nk; it.nq = a.Nq; it.nk = a.Nk; }
+    return it;
+}
+// The one-kernel backward reads the table in its EARLY forms only (the ones the packed entry points launch).  Every other form compiles the strided expressions, formed
+// at the point of use exactly as before: the 16-key-tile forms sit at 245 - 253 VGPRs with every SGPR taken, and per-item values kept live across an item -- even the
+// strided ones -- pushed them into scratch.
+#define ITQ0(IT, B) (EARLY ? (IT).q0 : (long)(B) * a.Nq)
+#define ITK0(IT, B) (EARLY ? (IT).k0 : (long)(B) * a.Nk)
+#define ITNQ(IT) (EARLY ? (IT).nq : a.Nq)
+#define ITNK(IT) (EARLY ? (IT).nk : a.Nk)
 
 // Head size DH = 64 (every tower of the contrastive path) or 128 (ViLBERT co-attention, vilbert.py:326-416 with bi_hidden_size 1024 / 8 heads):
 // token tiles [tokens][DH] with 2 DH-byte rows; the 16-B slot index of a row is XOR-swizzled so that BOTH access patterns sweep all 64 banks:
@@ -153,10 +173,11 @@ __device__ __forceinline__ bf16x8_t load_frag_global(const bf16_t* p) {
 __device__ __forceinline__ float grp_max(float v) { v = fmaxf(v, __shfl_xor(v, 16, 64)); return fmaxf(v, __shfl_xor(v, 32, 64)); }
 __device__ __forceinline__ float grp_sum(float v) { v += __shfl_xor(v, 16, 64); return v + __shfl_xor(v, 32, 64); }
 // key bias in the exp2 domain; padding keys get -inf
-__device__ __forceinline__ void stage_key_bias(float* kb, const AttnArgs& a, int b, int n_pad) {
+__device__ __forceinline__ void stage_key_bias(float* kb, const AttnArgs& a, int b, int n_pad, int nk) {
     for (int i = threadIdx.x; i < n_pad; i += ATTN_THREADS)
-        kb[i] = i < a.Nk ? (a.key_bias ? a.key_bias[(long)b * a.Nk + i] * LOG2E : 0.f) : -INFINITY;
+        kb[i] = i < nk ? (a.key_bias ? a.key_bias[(long)b * a.Nk + i] * LOG2E : 0.f) : -INFINITY;
 }
+__device__ __forceinline__ void stage_key_bias(float* kb, const AttnArgs& a, int b, int n_pad) { stage_key_bias(kb, a, b, n_pad, a.Nk); }
 
 // ---- forward ----------------------------------------------------------------------------------------
 // DROP: attention-probability dropout compiled in (a separate instantiation: the mask arithmetic in the inner loops costs registers
@@ -201,18 +222,19 @@ __global__ __launch_bounds__(ATTN_THREADS, DH == 64 ? 2 : 1) void attn_fwd_kerne
         if (lds_alloc & 0xfffu) for (int i = 0; i < a.fwd_stagger; ++i) __builtin_amdgcn_s_sleep(127);
     }
 #endif
-    stage_rows2<DH, NKP>(Ks, a.k + (long)b * a.Nk * a.ldk + h * DH, a.ldk, Vs, a.v + (long)b * a.Nk * a.ldv + h * DH, a.ldv, (ABL & 4) ? 0 : a.Nk, NKP);
-    stage_key_bias(kb, a, b, NKP);
+    const AttnItem it = attn_item(a, b);
+    stage_rows2<DH, NKP>(Ks, a.k + it.k0 * a.ldk + h * DH, a.ldk, Vs, a.v + it.k0 * a.ldv + h * DH, a.ldv, (ABL & 4) ? 0 : it.nk, NKP);
+    stage_key_bias(kb, a, b, NKP, it.nk);
     __syncthreads();
 
     const float scale2 = a.scale * LOG2E;
-    const int nqt = (a.Nq + 15) >> 4;
+    const int nqt = (it.nq + 15) >> 4;   // (packed: the query tiles past the item's length do not exist)
     const bool o_al16 = !(a.ldo & 7) && !((uintptr_t)a.o & 15);
     // the query fragments of a tile come straight from global memory: the NEXT tile's are requested before the current tile is
     // processed (PMC: 68 % of the wave cycles were spent parked on s_waitcnt with the loads issued at the point of use)
     auto q_ptr = [&](int qt) {
         const int qi = qt * 16 + l15;
-        return a.q + ((long)b * a.Nq + (qi < a.Nq ? qi : a.Nq - 1)) * a.ldq + h * DH + grp * 8;
+        return a.q + (it.q0 + (qi < it.nq ? qi : it.nq - 1)) * a.ldq + h * DH + grp * 8;
     };
     bf16x8_t nq[KM] = {};
     if (wave < nqt && !(ABL & 32)) {
@@ -222,7 +244,7 @@ __global__ __launch_bounds__(ATTN_THREADS, DH == 64 ? 2 : 1) void attn_fwd_kerne
     }
     for (int qt = wave; qt < nqt; qt += ATTN_THREADS / 64) {
         const int qi = qt * 16 + l15;
-        const int qrow = qi < a.Nq ? qi : a.Nq - 1;
+        const int qrow = qi < it.nq ? qi : it.nq - 1;
         bf16x8_t qf[KM];
 #pragma unroll
         for (int j = 0; j < KM; ++j) qf[j] = nq[j];
@@ -283,8 +305,8 @@ __global__ __launch_bounds__(ATTN_THREADS, DH == 64 ? 2 : 1) void attn_fwd_kerne
             for (int dt = 0; dt < DT; ++dt) keep_ += __uint_as_float(ow[dt].x) + __uint_as_float(ow[dt].y);
             if (keep_ == 1.2345f) a.lse[0] = keep_;
         } else {
-        store_rows_paired<DT>(a.o + ((long)b * a.Nq + qrow) * a.ldo + h * DH, ow, lane, grp, qi < a.Nq, o_al16);
-        if (grp == 0 && qi < a.Nq) a.lse[((long)b * a.heads + h) * a.Nq + qi] = sum > 0.f ? (m + LOG2F(sum)) * LN2 : -INFINITY;
+        store_rows_paired<DT>(a.o + (it.q0 + qrow) * a.ldo + h * DH, ow, lane, grp, qi < it.nq, o_al16);
+        if (grp == 0 && qi < it.nq) a.lse[((long)b * a.heads + h) * a.Nq + qi] = sum > 0.f ? (m + LOG2F(sum)) * LN2 : -INFINITY;
         }
     }
 }
@@ -984,8 +1006,8 @@ __device__ __forceinline__ void attn_dma_piece(char* tile, uint32_t tile_lds, co
                 g1_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(FUSED_KT(8), bf_, g1_, 0, 0, 0);                                              \
             }                                                                                                                               \
             const int qi_ = 32 * (C) + 16 * qqt + l15;                                                                                      \
-            if (qi_ < a.Nq)                                                                                                                 \
-                *reinterpret_cast<uint2*>(a.dq + ((long)b * a.Nq + qi_) * a.lddq + h * 64 + 16 * qdt + 4 * grp) =                           \
+            if (qi_ < ITNQ(it))                                                                                                                 \
+                *reinterpret_cast<uint2*>(a.dq + (ITQ0(it, b) + qi_) * a.lddq + h * 64 + 16 * qdt + 4 * grp) =                           \
                     make_uint2(pack_bf2((g0_[0] + g1_[0]) * a.scale, (g0_[1] + g1_[1]) * a.scale),                                          \
                                pack_bf2((g0_[2] + g1_[2]) * a.scale, (g0_[3] + g1_[3]) * a.scale));                                         \
             if constexpr (SUMS && !(SUMS & 16)) FUSED_QSUM_ACC(g0_, g1_);   /* (padding queries: their dS^T rows are exactly 0) */                           \
@@ -1042,15 +1064,17 @@ __global__ __launch_bounds__(ATTN_THREADS, 1) void attn_bwd_fused64_kernel(const
 #define FUSED_DMA_K(ITEM)                                                                                                                    \
     do {                                                                                                                                    \
         const int b_ = (ITEM) / a.heads, h_ = (ITEM) % a.heads;                                                                             \
+        const AttnItem it_ = (ITEM) == item ? it_cur : it_nxt;   /* (EARLY: table entries fetched an item ahead; otherwise unused) */                                                                                       \
         for (int pc_ = wave; pc_ < (HASE ? 36 : 4 * NKS); pc_ += ATTN_THREADS / 64)   /* (the rows the contractions read) */                \
-            attn_dma_piece(Ks, lds0 + (uint32_t)(Ks - smem), a.k + (long)b_ * a.Nk * a.ldk + h_ * 64, a.ldk, a.Nk, pc_, lane);              \
+            attn_dma_piece(Ks, lds0 + (uint32_t)(Ks - smem), a.k + ITK0(it_, b_) * a.ldk + h_ * 64, a.ldk, ITNK(it_), pc_, lane);              \
     } while (0)
     // chunk C of Q (waves 0 - 3) and dO (waves 4 - 7): one piece per wave
 #define FUSED_DMA_QD(ITEM, C, QB)   /* QB: byte offset of the destination Q tile (its dO tile follows it) */                                   \
     do {                                                                                                                                    \
         const int b_ = (ITEM) / a.heads, h_ = (ITEM) % a.heads;                                                                             \
-        if (wave < 4) attn_dma_piece(smem + (QB), lds0 + (uint32_t)(QB), a.q + (long)b_ * a.Nq * a.ldq + h_ * 64, a.ldq, a.Nq, 4 * (C) + wave, lane); \
-        else attn_dma_piece(smem + (QB) + NQP * 128, lds0 + (uint32_t)((QB) + NQP * 128), a.d_o + (long)b_ * a.Nq * a.lddo + h_ * 64, a.lddo, a.Nq, 4 * (C) + wave - 4, lane); \
+        const AttnItem it_ = (ITEM) == item ? it_cur : it_nxt;   /* (EARLY: table entries fetched an item ahead; otherwise unused) */                                                                                       \
+        if (wave < 4) attn_dma_piece(smem + (QB), lds0 + (uint32_t)(QB), a.q + ITQ0(it_, b_) * a.ldq + h_ * 64, a.ldq, ITNQ(it_), 4 * (C) + wave, lane); \
+        else attn_dma_piece(smem + (QB) + NQP * 128, lds0 + (uint32_t)((QB) + NQP * 128), a.d_o + ITQ0(it_, b_) * a.lddo + h_ * 64, a.lddo, ITNQ(it_), 4 * (C) + wave - 4, lane); \
     } while (0)
     // what an item needs in REGISTERS, requested while the previous item's dK / dV stores drain: its O rows in the staging pattern of the token tiles (thread -> row id >> 3,
     // 16-B slot id & 7, id = thread + 512 i) for D = rowsum(dO o O) -- dO comes out of the landed LDS tile --, its lse row, the V fragments and key biases of this wave's tiles
@@ -1061,24 +1085,25 @@ __global__ __launch_bounds__(ATTN_THREADS, 1) void attn_bwd_fused64_kernel(const
 #define FUSED_PREFETCH_REGS(ITEM)                                                                                                            \
     do {                                                                                                                                    \
         const int b_ = (ITEM) / a.heads, h_ = (ITEM) % a.heads;                                                                             \
+        const AttnItem it_ = (ITEM) == item ? it_cur : it_nxt;   /* (EARLY: table entries fetched an item ahead; otherwise unused) */                                                                                       \
         _Pragma("unroll") for (int i_ = 0; i_ < 5; ++i_) {                                                                                  \
             const int id_ = wave * 64 + lane + i_ * ATTN_THREADS, row_ = id_ >> 3;                                                          \
             po[i_] = make_uint4(0, 0, 0, 0);                                                                                                \
-            if (!(ABL & 16) && row_ < a.Nq) po[i_] = *reinterpret_cast<const uint4*>(a.o + ((long)b_ * a.Nq + row_) * a.ldo + h_ * 64 + (id_ & 7) * 8); \
+            if (!(ABL & 16) && row_ < ITNQ(it_)) po[i_] = *reinterpret_cast<const uint4*>(a.o + (ITQ0(it_, b_) + row_) * a.ldo + h_ * 64 + (id_ & 7) * 8); \
         }                                                                                                                                   \
         pl = -INFINITY;                                                                                                                     \
-        if (wave * 64 + lane < a.Nq) pl = a.lse[((long)b_ * a.heads + h_) * a.Nq + wave * 64 + lane];                                       \
+        if (wave * 64 + lane < ITNQ(it_)) pl = a.lse[((long)b_ * a.heads + h_) * a.Nq + wave * 64 + lane];                                       \
         _Pragma("unroll") for (int j_ = 0; j_ < (NKS <= 4 ? 1 : 2); ++j_) {                                                                 \
-            const int ki_ = (wave + 8 * j_) * 16 + (lane & 15), krow_ = ki_ < a.Nk ? ki_ : a.Nk - 1;                                        \
-            const bf16_t* vp_ = a.v + ((long)b_ * a.Nk + krow_) * a.ldv + h_ * 64 + (lane >> 4) * 8;                                        \
+            const int ki_ = (wave + 8 * j_) * 16 + (lane & 15), krow_ = ki_ < ITNK(it_) ? ki_ : ITNK(it_) - 1;                                        \
+            const bf16_t* vp_ = a.v + (ITK0(it_, b_) + krow_) * a.ldv + h_ * 64 + (lane >> 4) * 8;                                        \
             vfn[j_][0] = load_frag_global(vp_); vfn[j_][1] = load_frag_global(vp_ + 32);                                                    \
-            kbn[j_] = ki_ < a.Nk ? (a.key_bias ? a.key_bias[(long)b_ * a.Nk + ki_] : 0.f) : -INFINITY;   /* (x log2 e at the point of use: no wait here) */ \
+            kbn[j_] = ki_ < ITNK(it_) ? (a.key_bias ? a.key_bias[(long)b_ * a.Nk + ki_] : 0.f) : -INFINITY;   /* (x log2 e at the point of use: no wait here) */ \
         }                                                                                                                                   \
         if constexpr (HASE) {                                                                                                               \
-            const int ki_ = 256 + (lane & 15), krow_ = ki_ < a.Nk ? ki_ : a.Nk - 1;                                                         \
-            const bf16_t* vp_ = a.v + ((long)b_ * a.Nk + krow_) * a.ldv + h_ * 64 + (lane >> 4) * 8;                                        \
+            const int ki_ = 256 + (lane & 15), krow_ = ki_ < ITNK(it_) ? ki_ : ITNK(it_) - 1;                                                         \
+            const bf16_t* vp_ = a.v + (ITK0(it_, b_) + krow_) * a.ldv + h_ * 64 + (lane >> 4) * 8;                                        \
             vfEn[0] = load_frag_global(vp_); vfEn[1] = load_frag_global(vp_ + 32);                                                          \
-            kbEn = ki_ < a.Nk ? (a.key_bias ? a.key_bias[(long)b_ * a.Nk + ki_] : 0.f) : -INFINITY;                                         \
+            kbEn = ki_ < ITNK(it_) ? (a.key_bias ? a.key_bias[(long)b_ * a.Nk + ki_] : 0.f) : -INFINITY;                                         \
         }                                                                                                                                   \
     } while (0)
 
@@ -1107,6 +1132,13 @@ __global__ __launch_bounds__(ATTN_THREADS, 1) void attn_bwd_fused64_kernel(const
 #define FUSED_OPAQUE_LANE(x) int x = lane_w; asm volatile("" : "+v"(x))   /* (offsets derived from it are recomputed at the point of use, not kept alive from the top of the item) */
 #endif
     int item = blockIdx.x, cur = 0;
+    // EARLY (the forms the packed entry points launch): the table entries of this item and the next, each fetched one item before its first use -- as scalar loads at the
+    // points of use they put ~ 1 us of dependent latency into every 6-us item (0.483 -> 0.575 ms per launch at 1024 x 16 x 77)
+    AttnItem it_cur{}, it_nxt{};
+    if constexpr (EARLY) {
+        if (item < n_items) it_cur = attn_item(a, item / a.heads);
+        if (item + (int)gridDim.x < n_items) it_nxt = attn_item(a, (item + (int)gridDim.x) / a.heads);
+    }
     int pitem = -1;   // SUMS: the item whose partial sums sit in LDS
     if constexpr (PERSIST) {
         const int lane = lane_w;
@@ -1125,6 +1157,13 @@ __global__ __launch_bounds__(ATTN_THREADS, 1) void attn_bwd_fused64_kernel(const
 #endif
     const int lane = lane_o, l15 = lane & 15, grp = lane >> 4;
     const int b = item / a.heads, h = item % a.heads;
+    const AttnItem it = it_cur;
+    AttnItem it_nn{};   // the item after the next: requested now, needed at the start of the next item
+    if constexpr (EARLY) {
+        const int i2 = item + 2 * (int)gridDim.x;
+        if (i2 < n_items) it_nn = attn_item(a, i2 / a.heads);
+    }
+    (void)it;
     const int nxt = item + gridDim.x;
     const bool has_next = PERSIST && nxt < n_items;
     float* lse_s = stats;
@@ -1149,14 +1188,14 @@ __global__ __launch_bounds__(ATTN_THREADS, 1) void attn_bwd_fused64_kernel(const
         if (wave * 64 + lane < NQP) lse_s[wave * 64 + lane] = pl == -INFINITY ? -INFINITY : -(pl / a.scale);   // raw-score units, negated; fully masked / padding query: -inf -> p = 0
         wg_barrier_lds_only();
     } else {
-        const bf16_t* qbase = a.q + (long)b * a.Nq * a.ldq + h * 64;
-        const bf16_t* dobase = a.d_o + (long)b * a.Nq * a.lddo + h * 64;
-        const bf16_t* obase = a.o + (long)b * a.Nq * a.ldo + h * 64;
-        stage_rows2<64, 288>(Qs, qbase, a.ldq, Ds, dobase, a.lddo, a.Nq, NQP);
-        stage_rows<64, 288>(Ks, a.k + (long)b * a.Nk * a.ldk + h * 64, a.ldk, a.Nk, 288);
+        const bf16_t* qbase = a.q + ITQ0(it, b) * a.ldq + h * 64;
+        const bf16_t* dobase = a.d_o + ITQ0(it, b) * a.lddo + h * 64;
+        const bf16_t* obase = a.o + ITQ0(it, b) * a.ldo + h * 64;
+        stage_rows2<64, 288>(Qs, qbase, a.ldq, Ds, dobase, a.lddo, ITNQ(it), NQP);
+        stage_rows<64, 288>(Ks, a.k + ITK0(it, b) * a.ldk + h * 64, a.ldk, ITNK(it), 288);
         for (int i = threadIdx.x; i < NQP; i += ATTN_THREADS) {   // (as attn_bwd_dkv_kernel; padding queries: p = 0)
             float d = 0.f, l = INFINITY;
-            if (i < a.Nq) {
+            if (i < ITNQ(it)) {
                 l = a.lse[((long)b * a.heads + h) * a.Nq + i];
                 l = l == -INFINITY ? INFINITY : l / a.scale;
                 if constexpr (!(ABL & 16)) {
@@ -1179,15 +1218,15 @@ __global__ __launch_bounds__(ATTN_THREADS, 1) void attn_bwd_fused64_kernel(const
     // ---- the key tile beyond the sixteen resident ones
     if constexpr (HASE && !(ABL & 32)) {
         char* Pe = Sb;   // (the dS^T double buffer is free until the main loop)
-        const int ki = 256 + l15, krow = ki < a.Nk ? ki : a.Nk - 1;
-        const bf16_t* vp = a.v + ((long)b * a.Nk + krow) * a.ldv + h * 64 + grp * 8;
+        const int ki = 256 + l15, krow = ki < ITNK(it) ? ki : ITNK(it) - 1;
+        const bf16_t* vp = a.v + (ITK0(it, b) + krow) * a.ldv + h * 64 + grp * 8;
         const bf16x8_t kfE[2] = {frag_rows<64>(Ks, 256 + l15, grp), frag_rows<64>(Ks, 256 + l15, 4 + grp)};
         bf16x8_t vfE[2];
         float kbE;
         if constexpr (PERSIST) { vfE[0] = vfEn[0]; vfE[1] = vfEn[1]; kbE = kbEn * LOG2E; }
         else {
             vfE[0] = load_frag_global(vp); vfE[1] = load_frag_global(vp + 32);
-            kbE = ki < a.Nk ? (a.key_bias ? a.key_bias[(long)b * a.Nk + ki] * LOG2E : 0.f) : -INFINITY;
+            kbE = ki < ITNK(it) ? (a.key_bias ? a.key_bias[(long)b * a.Nk + ki] * LOG2E : 0.f) : -INFINITY;
         }
         for (int c = wave; c < nqc; c += ATTN_THREADS / 64) {   // (query tiles of pure padding: lse_s = -inf -> p = dS = 0 out of the same code)
             float p[2][4], ds[2][4];
@@ -1231,8 +1270,8 @@ __global__ __launch_bounds__(ATTN_THREADS, 1) void attn_bwd_fused64_kernel(const
             }
 #undef FUSED_E_STEP
             const float sc = is_k ? a.scale : 1.0f;
-            if (ki < a.Nk) {
-                bf16_t* dst = (is_k ? a.dk + ((long)b * a.Nk + ki) * a.lddk : a.dv + ((long)b * a.Nk + ki) * a.lddv) + h * 64 + 16 * dt + 4 * grp;
+            if (ki < ITNK(it)) {
+                bf16_t* dst = (is_k ? a.dk + (ITK0(it, b) + ki) * a.lddk : a.dv + (ITK0(it, b) + ki) * a.lddv) + h * 64 + 16 * dt + 4 * grp;
                 *reinterpret_cast<uint2*>(dst) = make_uint2(pack_bf2((g0[0] + g1[0]) * sc, (g0[1] + g1[1]) * sc), pack_bf2((g0[2] + g1[2]) * sc, (g0[3] + g1[3]) * sc));
             }
             if ((SUMS & 3) == 1 || ((SUMS & 3) == 2 && is_k)) {   // this tile's share of the token sums (padding keys: exactly 0); waves 0 - 3: dV, 4 - 7: dK (unscaled), head-dim tile dt
@@ -1252,15 +1291,15 @@ __global__ __launch_bounds__(ATTN_THREADS, 1) void attn_bwd_fused64_kernel(const
     f32x4_t dk[2][4], dv[2][4];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        const int ki = kt[j] * 16 + l15, krow = ki < a.Nk ? ki : a.Nk - 1;
-        const bf16_t* vp = a.v + ((long)b * a.Nk + krow) * a.ldv + h * 64 + grp * 8;
+        const int ki = kt[j] * 16 + l15, krow = ki < ITNK(it) ? ki : ITNK(it) - 1;
+        const bf16_t* vp = a.v + (ITK0(it, b) + krow) * a.ldv + h * 64 + grp * 8;
         kf[j][0] = frag_rows<64>(Ks, ki, grp);      // (rows >= Nk: zero, or a copy of the last row in the persistent form -- their probabilities are 0 either way)
         kf[j][1] = frag_rows<64>(Ks, ki, 4 + grp);
         if constexpr (PERSIST) { vf[j][0] = vfn[j][0]; vf[j][1] = vfn[j][1]; kbias[j] = kbn[j] * LOG2E; }
         else {
             vf[j][0] = load_frag_global(vp);
             vf[j][1] = load_frag_global(vp + 32);
-            kbias[j] = ki < a.Nk ? (a.key_bias ? a.key_bias[(long)b * a.Nk + ki] * LOG2E : 0.f) : -INFINITY;
+            kbias[j] = ki < ITNK(it) ? (a.key_bias ? a.key_bias[(long)b * a.Nk + ki] * LOG2E : 0.f) : -INFINITY;
         }
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) { dk[j][dt] = (f32x4_t){0.f, 0.f, 0.f, 0.f}; dv[j][dt] = (f32x4_t){0.f, 0.f, 0.f, 0.f}; }
@@ -1352,15 +1391,15 @@ __global__ __launch_bounds__(ATTN_THREADS, 1) void attn_bwd_fused64_kernel(const
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         if (j == 0 ? !tva : !tvb) continue;
-        const int ki = kt[j] * 16 + l15, krow = ki < a.Nk ? ki : a.Nk - 1;
+        const int ki = kt[j] * 16 + l15, krow = ki < ITNK(it) ? ki : ITNK(it) - 1;
         uint2 vw[4], kw[4];
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
             vw[dt] = make_uint2(pack_bf2(dv[j][dt][0], dv[j][dt][1]), pack_bf2(dv[j][dt][2], dv[j][dt][3]));
             kw[dt] = make_uint2(pack_bf2(dk[j][dt][0] * a.scale, dk[j][dt][1] * a.scale), pack_bf2(dk[j][dt][2] * a.scale, dk[j][dt][3] * a.scale));
         }
-        store_rows_paired<4>(a.dv + ((long)b * a.Nk + krow) * a.lddv + h * 64, vw, lane, grp, ki < a.Nk, dkv_al16);
-        store_rows_paired<4>(a.dk + ((long)b * a.Nk + krow) * a.lddk + h * 64, kw, lane, grp, ki < a.Nk, dkv_al16);
+        store_rows_paired<4>(a.dv + (ITK0(it, b) + krow) * a.lddv + h * 64, vw, lane, grp, ki < ITNK(it), dkv_al16);
+        store_rows_paired<4>(a.dk + (ITK0(it, b) + krow) * a.lddk + h * 64, kw, lane, grp, ki < ITNK(it), dkv_al16);
     }
     if constexpr (SUMS && !(SUMS & 32)) {
         // token sums of this wave's dK / dV tiles (lane: key l15, head-dim 16 dt + 4 grp + r; tiles the wave does not own are zero): closed over the 16 lanes of a DPP
@@ -1385,6 +1424,7 @@ __global__ __launch_bounds__(ATTN_THREADS, 1) void attn_bwd_fused64_kernel(const
     }
     if constexpr (PERSIST && !EARLY) { if (has_next) FUSED_PREFETCH_REGS(nxt); }   // (behind the stores: the accumulators' registers are free now; all of it lands under the K tile's latency)
     pitem = item;
+    if constexpr (EARLY) { it_cur = it_nxt; it_nxt = it_nn; }
     } while (PERSIST && (item += gridDim.x) < n_items);
     if constexpr (SUMS) {   // the last item's
         wg_barrier_lds_only();
@@ -1404,6 +1444,10 @@ __global__ __launch_bounds__(ATTN_THREADS, 1) void attn_bwd_fused64_kernel(const
 #undef FUSED_CHUNK_DQ
 #undef FUSED_SCORE_BLOCK
 #undef FUSED_EXP
+#undef ITQ0
+#undef ITK0
+#undef ITNQ
+#undef ITNK
 
 // ---- C ABI --------------------------------------------------------------------------------------------
 static bool attn_args_ok(const AttnArgs& a, int dh) {
@@ -1428,7 +1472,7 @@ static int attn_fwd_launch(const AttnArgs& a, hipStream_t stream) {
     static const char* av_env = ANTMMF_LAB_ENV("ANTMMF_ATTN_VARIANT");
     const int av = av_env ? atoi(av_env) : 0;
     if constexpr (DH == 64) {
-        if (!a.drop_thr && (nch == 7 || nch == 9) && (av & 4)) {   // (its padding mask covers the LAST 32-key tile only: the key count must fill the instantiated tile count)
+        if (!a.drop_thr && !a.items && (nch == 7 || nch == 9) && (av & 4)) {   // (its padding mask covers the LAST 32-key tile only: the key count must fill the instantiated tile count)
 #define FWD32K(N, HB, KB) do { const size_t lds = (size_t)(32 * N) * 256 + (32 * N) * 4 + 8 * 2 * 68 * 4; set_lds(attn_fwd32_kernel<N, HB, KB>, lds); \
             hipLaunchKernelGGL((attn_fwd32_kernel<N, HB, KB>), grid, block, lds, stream, a); } while (0)
 #define FWD32(N, HB) do { if (av & 2) FWD32K(N, HB, 2); else FWD32K(N, HB, 1); } while (0)   /* variant bit 1: 64-key softmax blocks */
@@ -1444,7 +1488,7 @@ static int attn_fwd_launch(const AttnArgs& a, hipStream_t stream) {
     if constexpr (DH == 64) {
         static const char* fa_env = ANTMMF_LAB_ENV("ANTMMF_ATTN_FWD_ABL");   // timing-only ablations of the 257-token forward (wrong results)
         const int fa = fa_env ? atoi(fa_env) : 0;
-        if (fa && nch == 9 && !a.drop_thr) {
+        if (fa && nch == 9 && !a.drop_thr && !a.items) {
             const size_t lds = (size_t)(32 * 9) * (4 * DH) + (32 * 9) * 4;
 #define FWDA(A) case A: set_lds(attn_fwd_kernel<9, false, 64, A>, lds); hipLaunchKernelGGL((attn_fwd_kernel<9, false, 64, A>), grid, block, lds, stream, a); return antmmf_check_launch();
             switch (fa) { FWDA(1) FWDA(2) FWDA(4) FWDA(8) FWDA(16) FWDA(32) FWDA(24) FWDA(25) FWDA(38) FWDA(63) FWDA(27) default: break; }
@@ -1469,7 +1513,7 @@ static int attn_bwd_launch(const AttnArgs& a, hipStream_t stream) {
         bool fused = attn_fused_ok(a);
 #ifdef ANTMMF_LAB
         static const char* bv_env = ANTMMF_LAB_ENV("ANTMMF_ATTN_VARIANT");   // bit 3: the two-kernel backward everywhere (same-box A/B)
-        if (bv_env && (atoi(bv_env) & 8) && !a.sums) fused = false;
+        if (bv_env && (atoi(bv_env) & 8) && !a.sums && !a.items) fused = false;
 #endif
         if (fused) {
 #ifdef ANTMMF_LAB
@@ -1481,6 +1525,7 @@ static int attn_bwd_launch(const AttnArgs& a, hipStream_t stream) {
             const bool persist = (nkt <= 16 || nqp == 288) && attn_fused_lds_bytes(a.Nq, a.Nk, false, sm) <= 160 * 1024;   // (a 17th key tile with other query counts: run-time chunk loops, spills in the persistent form)
             const bool early = persist && nkt <= 8 && attn_fused_lds_bytes(a.Nq, a.Nk, true, sm) <= 160 * 1024;
             const size_t lds = attn_fused_lds_bytes(a.Nq, a.Nk, early, sm);
+            if (a.items && !early) return ANTMMF_EINVAL;   // (the item table is read by the double-buffered persistent forms only -- ITQ0 ... ITNK --: attn_packed_ok)
             unsigned pwgs = 256u;
 #ifdef ANTMMF_LAB
             static const char* pw_env = ANTMMF_LAB_ENV("ANTMMF_ATTN_PERSIST_WGS");   // lab / emulator tests: a small grid makes every workgroup walk several items
@@ -1542,6 +1587,7 @@ static int attn_bwd_launch(const AttnArgs& a, hipStream_t stream) {
             return antmmf_check_launch();
         }
     }
+    if (a.items) return ANTMMF_EINVAL;   // (no packed form of the two-kernel backward)
 #define BWDQ_K(KERN, LDS) do { set_lds(KERN, LDS); hipLaunchKernelGGL(KERN, grid, block, LDS, stream, a); } while (0)
 #define BWDQ(N) do { const size_t lds = (size_t)(32 * N) * (4 * DH) + (32 * N) * 4; \
         if constexpr (DH == 64) { if (a.drop_thr) BWDQ_K((attn_bwd_dq64_kernel<N, true>), lds); else BWDQ_K((attn_bwd_dq64_kernel<N, false>), lds); } \
@@ -1633,6 +1679,58 @@ extern "C" int antmmf_attention_bwd_sums(const void* q, const void* k, const voi
         return ANTMMF_EINVAL;
     if (!attn_fused_ok(a)) return ANTMMF_EINVAL;
     return attn_bwd_launch<64>(a, stream);
+}
+
+// ---- token-packed self-attention ------------------------------------------------------------------------------------------------------------------
+// q | k | v | o (| dO | dq | dk | dv) are [T, heads * 64] matrices (views of packed projections through their row strides) that hold only real tokens, item after
+// item; items[2 b] = first row of item b, items[2 b + 1] = its length, 1 ... n_max.  n_max is the longest ALLOWED item (it sizes tiles and launches and is the row
+// length of lse [B, heads, n_max]), not the longest present one.  Rows outside every item -- and lse entries at or beyond an item's length -- are neither read nor
+// written.  Same kernels as the strided entry points (AttnArgs::items): an item computes exactly what the strided form computes for it under a key_bias that is -inf
+// from its length on.  Served: head size 64, 33 ... 128 tokens (the forward's resident tiles and the double-buffered persistent one-kernel backward), no dropout.
+static bool attn_packed_ok(int head_dim, int n_max) {
+    if (head_dim != 64 || n_max <= 32 || n_max > 128) return false;
+    AttnArgs a{};
+    float dummy = 0.f;
+    a.Nq = a.Nk = n_max; a.sums = &dummy;
+    return attn_fused_ok(a) && attn_fused_lds_bytes(n_max, n_max, true, true) <= 160 * 1024;
+}
+extern "C" int antmmf_attention_packed_ok(int head_dim, int n_max) { return attn_packed_ok(head_dim, n_max) ? 1 : 0; }
+extern "C" int antmmf_attention_fwd_packed(const void* q, const void* k, const void* v, const int* items, void* o, float* lse, int B, int heads, int n_max,
+                                           long ldq, long ldk, long ldv, long ldo, float scale, hipStream_t stream) {
+    AttnArgs a{};
+    a.drop_thr = 0; a.drop_scale = 1.0f;
+    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (bf16_t*)o; a.lse = lse; a.items = items;
+    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.B = B; a.heads = heads; a.Nq = n_max; a.Nk = n_max; a.scale = scale;
+    if (!q || !k || !v || !o || !lse || !items || !attn_args_ok(a, 64) || !attn_packed_ok(64, n_max)) return ANTMMF_EINVAL;
+    return attn_fwd_launch<64>(a, stream);
+}
+static int attn_bwd_packed(const void* q, const void* k, const void* v, const int* items, const void* o, const float* lse, const void* d_o, void* dq, void* dk,
+                           void* dv, float* sums, int want_dv, int B, int heads, int n_max, long ldq, long ldk, long ldv, long ldo, long lddo, long lddq,
+                           long lddk, long lddv, float scale, hipStream_t stream) {
+    AttnArgs a{};
+    a.drop_thr = 0; a.drop_scale = 1.0f;
+    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (bf16_t*)const_cast<void*>(o); a.items = items;
+    a.lse = const_cast<float*>(lse); a.d_o = (const bf16_t*)d_o; a.dq = (bf16_t*)dq; a.dk = (bf16_t*)dk; a.dv = (bf16_t*)dv;
+    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.lddo = lddo; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
+    a.B = B; a.heads = heads; a.Nq = n_max; a.Nk = n_max; a.scale = scale; a.sums = sums; a.sums_v = want_dv ? 1 : 0;
+    if (!q || !k || !v || !o || !lse || !d_o || !dq || !dk || !dv || !items || !attn_args_ok(a, 64) || (lddo & 7) || (lddq & 3) || (lddk & 3) || (lddv & 3) || (ldo & 7))
+        return ANTMMF_EINVAL;
+    if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)d_o | (uintptr_t)o) & 15) || (((uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) & 7))
+        return ANTMMF_EINVAL;
+    if (!attn_packed_ok(64, n_max)) return ANTMMF_EINVAL;
+    return attn_bwd_launch<64>(a, stream);
+}
+extern "C" int antmmf_attention_bwd_packed(const void* q, const void* k, const void* v, const int* items, const void* o, const float* lse, const void* d_o, void* dq,
+                                           void* dk, void* dv, int B, int heads, int n_max, long ldq, long ldk, long ldv, long ldo, long lddo, long lddq, long lddk,
+                                           long lddv, float scale, hipStream_t stream) {
+    return attn_bwd_packed(q, k, v, items, o, lse, d_o, dq, dk, dv, nullptr, 0, B, heads, n_max, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv, scale, stream);
+}
+// ... plus the per-item token sums of dQ | dK (| dV) of antmmf_attention_bwd_sums: sums [B, 3 * heads * 64]
+extern "C" int antmmf_attention_bwd_sums_packed(const void* q, const void* k, const void* v, const int* items, const void* o, const float* lse, const void* d_o,
+                                                void* dq, void* dk, void* dv, float* sums, int want_dv, int B, int heads, int n_max, long ldq, long ldk, long ldv,
+                                                long ldo, long lddo, long lddq, long lddk, long lddv, float scale, hipStream_t stream) {
+    if (!sums) return ANTMMF_EINVAL;
+    return attn_bwd_packed(q, k, v, items, o, lse, d_o, dq, dk, dv, sums, want_dv, B, heads, n_max, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv, scale, stream);
 }
 
 // ---- key importance: column sums of the attention probabilities --------------------------------------------------------------------------------

@@ -339,14 +339,23 @@ extern "C" int antmmf_split_tokens(const void* dx, void* dpatch, long B, int G, 
 // ------------------------------------------------------------------ embedding gather (sum of up to three tables) and scatter-add of its gradient
 // out[r] = word[ids[r]] (+ pos[pos_ids ? pos_ids[r] : pos_offset + r % seq]) (+ type[type_ids ? type_ids[r] : 0]); padded rows can be zeroed (M2: encoder.py:440)
 // reference: BertEmbeddings clip_text_encoder.py:36-60; TextEmbedding / PositionalEmbedding embedding.py:86-110
+// Token-packed output (antmmf_embed_gather_packed): `items` = (first packed row, length) per sequence; token n of sequence b goes to out row items[2 b] + n with position n,
+// tokens at or beyond the length are not written at all -- the padded [B, seq, d] tensor never exists.
 __global__ __launch_bounds__(256) void embed_gather_kernel(const long* __restrict__ ids, const float* __restrict__ word, const float* __restrict__ pos,
                                                            const float* __restrict__ type, const long* __restrict__ type_ids,
                                                            const unsigned char* __restrict__ zero_rows, bf16_t* __restrict__ out,
-                                                           long rows, int seq, int d, int pos_offset) {
+                                                           long rows, int seq, int d, int pos_offset, const int* __restrict__ items) {
     const int dv = d >> 3;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < rows * dv; i += (long)gridDim.x * 256) {
         const int v = (int)(i % dv);
         const long r = i / dv;
+        long orow = r;
+        if (items) {
+            const long b = r / seq;
+            const int n = (int)(r - b * seq);
+            if (n >= items[2 * b + 1]) continue;
+            orow = (long)items[2 * b] + n;
+        }
         float o[8], t[8];
         ld8<float>(word + ids[r] * d + v * 8, o);
         if (pos) { ld8<float>(pos + (long)(pos_offset + (int)(r % seq)) * d + v * 8, t);
@@ -358,14 +367,23 @@ __global__ __launch_bounds__(256) void embed_gather_kernel(const long* __restric
         if (zero_rows && zero_rows[r]) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = 0.f; }
-        st8<bf16_t>(out + r * d + v * 8, o);
+        st8<bf16_t>(out + orow * d + v * 8, o);
     }
 }
 extern "C" int antmmf_embed_gather(const long* ids, const float* word, const float* pos, const float* type, const long* type_ids,
                                    const unsigned char* zero_rows, void* out, long rows, int seq, int d, int pos_offset, hipStream_t s) {
     if (!ids || !word || !out || rows < 0 || seq <= 0 || d <= 0 || (d & 7)) return ANTMMF_EINVAL;
     if (!rows) return ANTMMF_OK;
-    hipLaunchKernelGGL(embed_gather_kernel, dim3(ew_grid(rows * (d / 8))), dim3(256), 0, s, ids, word, pos, type, type_ids, zero_rows, (bf16_t*)out, rows, seq, d, pos_offset);
+    hipLaunchKernelGGL(embed_gather_kernel, dim3(ew_grid(rows * (d / 8))), dim3(256), 0, s, ids, word, pos, type, type_ids, zero_rows, (bf16_t*)out, rows, seq, d, pos_offset, (const int*)nullptr);
+    return antmmf_check_launch();
+}
+// ids [rows = B * seq] padded as the loader delivers them; out: the packed [T, d] matrix (T >= items[2 B - 2] + items[2 B - 1]; rows that belong to no item are not touched)
+extern "C" int antmmf_embed_gather_packed(const long* ids, const float* word, const float* pos, const float* type, const int* items, void* out, long rows, int seq, int d,
+                                          int pos_offset, hipStream_t s) {
+    if (!ids || !word || !out || !items || rows < 0 || seq <= 0 || d <= 0 || (d & 7) || rows % seq) return ANTMMF_EINVAL;
+    if (!rows) return ANTMMF_OK;
+    hipLaunchKernelGGL(embed_gather_kernel, dim3(ew_grid(rows * (d / 8))), dim3(256), 0, s, ids, word, pos, type, (const long*)nullptr, (const unsigned char*)nullptr, (bf16_t*)out,
+                       rows, seq, d, pos_offset, items);
     return antmmf_check_launch();
 }
 // dtable[idx[r]] += dx[r]  (fp32 atomics; idx == NULL means idx[r] = offset + r % seq, i.e. the position table)
@@ -422,7 +440,7 @@ extern "C" int antmmf_embed_scatter_add_sorted(const void* dx, const long* sorte
 // atomics above were 1024 fp32 atomic adds per output element at the bench size (1.19 ms per call).  Here a thread owns one (position, 8-column vector) and
 // walks a slice of the batch in registers; one atomic per slice and element closes it (gridDim.y slices: 64 x fewer atomics, coalesced 16-B row reads).
 __global__ __launch_bounds__(256) void embed_scatter_pos_kernel(const bf16_t* __restrict__ dx, const unsigned char* __restrict__ skip_rows, float* __restrict__ dtable,
-                                                                long nseq, int seq, int d, int offset) {
+                                                                long nseq, int seq, int d, int offset, const int* __restrict__ items) {
     const int dv = d >> 3;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= seq * dv) return;
@@ -430,8 +448,11 @@ __global__ __launch_bounds__(256) void embed_scatter_pos_kernel(const bf16_t* __
     const long per = (nseq + gridDim.y - 1) / gridDim.y, b0 = blockIdx.y * per, b1 = b0 + per < nseq ? b0 + per : nseq;
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (long b = b0; b < b1; ++b) {
-        const long r = b * seq + pos;
-        if (skip_rows && skip_rows[r]) continue;
+        long r = b * seq + pos;
+        if (items) {   // token-packed dx: sequence b's position `pos` is row items[2 b] + pos, if it has one
+            if (pos >= items[2 * b + 1]) continue;
+            r = (long)items[2 * b] + pos;
+        } else if (skip_rows && skip_rows[r]) continue;
         float g[8];
         ld8<bf16_t>(dx + r * d + v * 8, g);
 #pragma unroll
@@ -449,10 +470,19 @@ extern "C" int antmmf_embed_scatter_add(const void* dx, const long* idx, const u
         const long nseq = rows / seq;
         const int slices = (int)(nseq / 16 < 64 ? nseq / 16 : 64);
         hipLaunchKernelGGL(embed_scatter_pos_kernel, dim3((unsigned)((seq * (d >> 3) + 255) / 256), (unsigned)slices), dim3(256), 0, s, (const bf16_t*)dx, skip_rows, dtable,
-                           nseq, seq, d, offset);
+                           nseq, seq, d, offset, (const int*)nullptr);
         return antmmf_check_launch();
     }
     hipLaunchKernelGGL(embed_scatter_kernel, dim3(ew_grid(rows * (d / 8))), dim3(256), 0, s, (const bf16_t*)dx, idx, skip_rows, dtable, rows, seq, d, offset);
+    return antmmf_check_launch();
+}
+// position-table gradient out of a token-packed dx: dtable[offset + n] += sum over the sequences b with length > n of dx[items[2 b] + n]
+extern "C" int antmmf_embed_scatter_add_pos_packed(const void* dx, const int* items, float* dtable, long nseq, int seq, int d, int offset, hipStream_t s) {
+    if (!dx || !items || !dtable || nseq < 0 || seq <= 0 || d <= 0 || (d & 7)) return ANTMMF_EINVAL;
+    if (!nseq) return ANTMMF_OK;
+    const int slices = (int)(nseq / 16 < 1 ? 1 : (nseq / 16 < 64 ? nseq / 16 : 64));
+    hipLaunchKernelGGL(embed_scatter_pos_kernel, dim3((unsigned)((seq * (d >> 3) + 255) / 256), (unsigned)slices), dim3(256), 0, s, (const bf16_t*)dx,
+                       (const unsigned char*)nullptr, dtable, nseq, seq, d, offset, items);
     return antmmf_check_launch();
 }
 

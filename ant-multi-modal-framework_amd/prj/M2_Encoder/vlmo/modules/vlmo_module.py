@@ -99,6 +99,27 @@ def get_pretrained_tokenizer(tokenizer_type, from_pretrained):
     raise NotImplementedError(f"get_pretrained_tokenizer: {tokenizer_type!r} (GLMChineseTokenizer | BertTokenizer)")
 
 
+class _LazyFeats(dict):
+    """A feature dict some of whose entries are produced on first access (`text_feats` of the packed text tower: the padded per-token tensor that the ITC loss never
+    reads)."""
+
+    def __init__(self, values, **lazy):
+        super().__init__(values)
+        self._lazy = dict(lazy)
+
+    def __missing__(self, key):
+        if key in self._lazy:
+            self[key] = self._lazy.pop(key)()
+            return dict.__getitem__(self, key)
+        raise KeyError(key)
+
+    def __contains__(self, key):
+        return dict.__contains__(self, key) or key in self._lazy
+
+    def get(self, key, default=None):
+        return self[key] if key in self else default
+
+
 class VLMo(nn.Module):
     def __init__(self, config):
         super().__init__()
@@ -114,6 +135,7 @@ class VLMo(nn.Module):
             share_attn=config.get("share_attn", False), deepnorm=config.get("deepnorm", False), mask_ratio=config.get("mask_ratio", 0),
             max_text_len=config.get("max_text_len", 52), one_attn=config.get("one_attn", False), **kwargs)
         self.num_features = args.encoder_embed_dim
+        self._head_dim = args.encoder_embed_dim // args.encoder_attention_heads   # (the packed text path serves head size 64 only: HF.packed_text_begin)
         self.out_features = config["out_embed_dim"]
         self.patch_size = config["patch_size"]
         self.num_frames = config.get("num_frames", 1)
@@ -162,9 +184,19 @@ class VLMo(nn.Module):
         return self.load_state_dict(state_dict, strict=False)
 
     # ------------------------------------------------------------------ towers (reference :323-405)
-    def infer_text(self, batch, mask_text=False):
+    def infer_text(self, batch, mask_text=False, packed_plan=None):
+        """Ragged captions run token-packed (no padding rows are computed: HF.PackedText) when the mask is a prefix mask of a width the packed attention kernels
+        serve; any other batch takes the padded path.  `packed_plan`: an HF.packed_text_begin(text_masks) the caller issued earlier (compute_itc does, ahead of the
+        image tower, so that the row count is on the host by now); None: issued here.  Packed, `text_feats` is unpacked on first access (padded rows zero)."""
         assert not mask_text, "MLM is outside the ITC path"
         text_ids, text_masks = batch["text_ids"], batch["text_masks"]
+        text = HF.packed_text_finish(packed_plan if packed_plan is not None else HF.packed_text_begin(text_masks, self._head_dim))
+        if text is not None:
+            lffn = self.backbone(textual_tokens=text_ids, packed=text)["encoder_out"]
+            vlffn = self.backbone_vl(token_embeddings=lffn, multiway_split_position=-1, packed=text)["encoder_out"]
+            cls_feats = HF.l2_normalize(self.itc_text_proj(lffn.index_select(0, text.row0)), eps=0.0)
+            cls_vlffn_feats = HF.l2_normalize(self.itc_vl_text_proj(vlffn.index_select(0, text.row0)), eps=0.0)
+            return _LazyFeats({"cls_feats": cls_feats, "cls_vlffn_feats": cls_vlffn_feats}, text_feats=lambda: text.unpack(lffn))
         pad = 1 - text_masks
         lffn = self.backbone(textual_tokens=text_ids, text_padding_position=pad)["encoder_out"]
         vlffn = self.backbone_vl(token_embeddings=lffn, encoder_padding_mask=pad.bool(), multiway_split_position=-1)["encoder_out"]
@@ -185,7 +217,10 @@ class VLMo(nn.Module):
 
     # ------------------------------------------------------------------ training step (this build's; see module docstring)
     def compute_itc(self, batch):
-        oi, ot = self.infer_image(batch), self.infer_text(batch)
+        # the text tower's row count (sum of the caption lengths) has to reach the host: its tiny copy goes out on a side stream NOW, ahead of the image tower
+        plan = HF.packed_text_begin(batch["text_masks"], self._head_dim)
+        oi = self.infer_image(batch)
+        ot = self.infer_text(batch, packed_plan=plan) if plan is not None else self.infer_text(batch)
         l1, l2 = contrastive.clip_itc_pair_sharded(oi["cls_feats"], ot["cls_feats"], self.logit_scale,
                                                    oi["cls_vlffn_feats"], ot["cls_vlffn_feats"], self.logit_vl_scale)
         return {"losses": {"itc_loss": 0.5 * l1, "itc_vl_loss": 0.5 * l2}, "image": oi, "text": ot}

@@ -39,10 +39,12 @@ class EncoderLayer(nn.Module):
                     w2=f.fc2.weight, b2=f.fc2.bias)
 
     def forward(self, x, encoder_padding_mask=None, attn_mask=None, rel_pos=None, multiway_split_position=None,
-                incremental_state=None, key_bias=None):
+                incremental_state=None, key_bias=None, packed=None):
         if attn_mask is not None or rel_pos is not None or incremental_state is not None:
             raise NotImplementedError("attn_mask / rel_pos / incremental decoding are outside the ITC path")
         br = branch_of(-1 if multiway_split_position is None else multiway_split_position)
+        if packed is not None:   # token-packed [rows, d] input: the item table replaces the padding mask
+            return HF.transformer_layer(x, self._spec, self._params(br), packed=packed), None
         if key_bias is None and encoder_padding_mask is not None:
             key_bias = torch.zeros(encoder_padding_mask.shape, dtype=torch.float32, device=x.device).masked_fill_(
                 encoder_padding_mask.bool(), float("-inf"))
@@ -72,12 +74,22 @@ class Encoder(nn.Module):
                     p.data.mul_(init_scale)
 
     def forward(self, src_tokens=None, encoder_padding_mask=None, attn_mask=None, return_all_hiddens=False, token_embeddings=None,
-                multiway_split_position=None, features_only=False, incremental_state=None, positions=None, pos_added=False, **kwargs):
+                multiway_split_position=None, features_only=False, incremental_state=None, positions=None, pos_added=False, packed=None, **kwargs):
         """token_embeddings [B, N, d] bf16.  `pos_added` tells that the caller's fused embedding kernel already added
-        this encoder's positional embedding and zeroed the padded rows (BEiT3 does)."""
+        this encoder's positional embedding and zeroed the padded rows (BEiT3 does).
+        `packed` (antmmf.hip.functional.PackedText): token_embeddings is the token-packed [rows, d] matrix of a ragged batch with positions already added; the
+        padding mask is not consulted (the item table carries it) and `encoder_out` is packed too."""
         assert token_embeddings is not None and attn_mask is None and incremental_state is None
         x = token_embeddings
         br = branch_of(-1 if multiway_split_position is None else multiway_split_position)
+        if packed is not None:
+            assert x.dim() == 2 and not return_all_hiddens, "packed input: [rows, d], no hidden-state list"
+            for layer in self.layers:
+                x, _ = layer(x, multiway_split_position=multiway_split_position, packed=packed)
+            ln = self.layer_norm.pick(br)
+            x = HF.layer_norm(x, ln.weight, ln.bias, ln.eps)
+            return {"encoder_out": x, "encoder_embedding": token_embeddings, "encoder_padding_mask": encoder_padding_mask, "encoder_states": [],
+                    "l_aux": [None] * len(self.layers), "multiway_split_position": multiway_split_position, "packed": packed}
         if not pos_added:
             if self.embed_positions is not None:
                 n = x.shape[1]

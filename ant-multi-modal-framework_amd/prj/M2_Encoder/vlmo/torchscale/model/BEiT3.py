@@ -21,7 +21,7 @@ class BEiT3(nn.Module):
         self.encoder = Encoder(args, embed_tokens=None, embed_positions=embed_positions, output_projection=None)
 
     def forward(self, textual_tokens=None, visual_tokens=None, text_padding_position=None, attn_mask=None,
-                vision_masked_position=None, incremental_state=None, positions=None, image_shift=0.0, image_scale=1.0):
+                vision_masked_position=None, incremental_state=None, positions=None, image_shift=0.0, image_scale=1.0, packed=None):
         assert (textual_tokens is None) != (visual_tokens is None), "ITC towers take one modality at a time"
         assert attn_mask is None and vision_masked_position is None and incremental_state is None and positions is None
         if textual_tokens is None:
@@ -30,6 +30,9 @@ class BEiT3(nn.Module):
             pos = self.encoder.embed_positions.A.weight[2:n + 2]
             x = HF.patch_embed(visual_tokens, ve.proj.weight, ve.proj.bias, ve.cls_token, pos, ve.patch_size[0], image_shift, image_scale)
             return self.encoder(token_embeddings=x, encoder_padding_mask=None, multiway_split_position=-1, pos_added=True)
+        if packed is not None:   # ragged captions as one token-packed matrix (HF.PackedText): the embedding kernel writes it directly, no padded tensor exists
+            x = HF.embed_packed(textual_tokens, self.text_embed.weight, self.encoder.embed_positions.B.weight, packed, pos_offset=2)
+            return self.encoder(token_embeddings=x, encoder_padding_mask=None, multiway_split_position=0, pos_added=True, packed=packed)
         pad = None
         zero_rows = None
         if text_padding_position is not None:

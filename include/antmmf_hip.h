@@ -128,6 +128,12 @@ int antmmf_embed_gather(const int64_t* ids, const float* word, const float* pos,
 /* ---- dtable[idx ? idx[r] : offset + r % seq] += dx[r]  (fp32 atomics; rows flagged in skip_rows are skipped). */
 int antmmf_embed_scatter_add(const void* dx, const int64_t* idx, const unsigned char* skip_rows, float* dtable,
                              int64_t rows, int seq, int d, int offset, antmmf_stream_t stream);
+/* Token-packed embedding: ids stay the padded [rows = B * seq] the loader delivers; token n < items[b][1] of sequence b is written to row items[b][0] + n of the
+ * packed out [T, d] with position pos_offset + n, everything else is not written (no padded [B, seq, d] tensor exists).  The position table's gradient out of a
+ * packed dx: dtable[offset + n] += sum over the sequences longer than n of dx[items[b][0] + n].  (The word table's takes the sorted form with packed source rows.) */
+int antmmf_embed_gather_packed(const int64_t* ids, const float* word, const float* pos, const float* type, const int32_t* items, void* out, int64_t rows,
+                               int seq, int d, int pos_offset, antmmf_stream_t stream);
+int antmmf_embed_scatter_add_pos_packed(const void* dx, const int32_t* items, float* dtable, int64_t nseq, int seq, int d, int offset, antmmf_stream_t stream);
 /* The word-table gradient without atomics: sorted_idx = the token ids in ascending order (rows to skip carry an id >= n_table), src_row = the row of dx each entry came
  * from (the sort's permutation).  One wave per run of equal ids sums the run and adds it to its table row: a single writer per row. */
 int antmmf_embed_scatter_add_sorted(const void* dx, const int64_t* sorted_idx, const int64_t* src_row, float* dtable, int64_t rows, int64_t n_table, int d,
@@ -243,6 +249,23 @@ int antmmf_attention_bwd_sums(const void* q, const void* k, const void* v, const
                               const float* lse, const void* d_o, void* dq, void* dk, void* dv, float* sums, int want_dv, int B, int heads,
                               int Nq, int Nk, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t lddo, int64_t lddq,
                               int64_t lddk, int64_t lddv, float scale, antmmf_stream_t stream);
+
+/* Token-packed self-attention (the M2 text tower without its caption padding).  q | k | v | o (| d_o | dq | dk | dv) are [T, heads * 64] bf16 matrices
+ * (views of a packed [T, 3d] projection through their row strides) holding only real tokens, item after item; items = int32 [B][2]: (first row, length) of
+ * every batch item, 1 <= length <= n_max.  n_max is the longest ALLOWED item (tile counts, launch size, and the row length of lse [B, heads, n_max]).
+ * An item computes exactly what the strided entry points compute for it under a key_bias that is -inf from its length on; rows of no item, and lse
+ * entries at or beyond an item's length, are neither read nor written.  antmmf_attention_packed_ok: 1 for the served shapes (head size 64,
+ * 33 ... 128 tokens, no dropout); the other entry points return ANTMMF_EINVAL for anything else.  sums: as antmmf_attention_bwd_sums. */
+int antmmf_attention_packed_ok(int head_dim, int n_max);
+int antmmf_attention_fwd_packed(const void* q, const void* k, const void* v, const int32_t* items, void* o, float* lse, int B, int heads, int n_max,
+                                int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, float scale, antmmf_stream_t stream);
+int antmmf_attention_bwd_packed(const void* q, const void* k, const void* v, const int32_t* items, const void* o, const float* lse, const void* d_o,
+                                void* dq, void* dk, void* dv, int B, int heads, int n_max, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo,
+                                int64_t lddo, int64_t lddq, int64_t lddk, int64_t lddv, float scale, antmmf_stream_t stream);
+int antmmf_attention_bwd_sums_packed(const void* q, const void* k, const void* v, const int32_t* items, const void* o, const float* lse, const void* d_o,
+                                     void* dq, void* dk, void* dv, float* sums, int want_dv, int B, int heads, int n_max, int64_t ldq, int64_t ldk,
+                                     int64_t ldv, int64_t ldo, int64_t lddo, int64_t lddq, int64_t lddk, int64_t lddv, float scale,
+                                     antmmf_stream_t stream);
 
 /* dropout_p > 0: attention-probability dropout (BertSelfAttention, modeling_bert.py:157) with a counter-based mask
  * keep(seed, ((b * heads + h) * Nq + q) * Nk + k) that forward and backward regenerate identically (nothing is stored);
