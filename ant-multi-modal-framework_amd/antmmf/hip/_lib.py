@@ -79,6 +79,7 @@ _SIGNATURES = {
     "antmmf_pair_wsum": [P, P, P, I, I, I, P],
     "antmmf_pair_outer": [P, P, P, I, I, I, P],
     "antmmf_tis_keep": [P, F, P, I, I, P],
+    "antmmf_tpmcl_limits": [P, P, P],
     "antmmf_negnce_fwd": [P, P, I, I, I, F, F, P, P, P, P, P],
     "antmmf_negnce_bwd": [P, P, P, P, I, I, I, F, F, P, I, P],
     "antmmf_resize_bicubic_u8": [P, L, P, I, I, I, I, I, I, P, P, P, P, I, P],

@@ -3,6 +3,7 @@
 Every wrapper validates device / dtype / layout, passes raw pointers + torch's current HIP stream and
 raises on a non-zero return code.  PyTorch is used for memory and streams only.
 """
+import ctypes
 
 import torch
 
@@ -853,8 +854,8 @@ def token_weight_bwd(feat, w, p, dout, dw, dbias=None, want_dfeat=True):
         _f32c(t, n)
     N, T, D = feat.shape
     scratch = _TW_SCRATCH.get(feat.device)
-    if scratch is None or scratch.numel() < 512 * (D + 1):
-        scratch = torch.empty(512 * 1025, dtype=torch.float32, device=feat.device)
+    if scratch is None or scratch.numel() < 512 * (D + 1):   # [G <= 512][D + 1] partial sums: grown when a wider D arrives
+        scratch = torch.empty(512 * (max(D, 1024) + 1), dtype=torch.float32, device=feat.device)
         _TW_SCRATCH[feat.device] = scratch
     dfeat = torch.empty_like(feat) if want_dfeat else None
     _rc(_lib.load().antmmf_token_weight_bwd(_p(feat), _p(w), _p(p), _p(dout), _p(dfeat), _p(dw), _p(dbias), _p(scratch), scratch.numel(), N, T, D,
@@ -901,6 +902,17 @@ def tis_keep(w, thresh):
     keep = torch.empty_like(w)
     _rc(_lib.load().antmmf_tis_keep(_p(w), float(thresh), _p(keep), R, T, _stream()), "antmmf_tis_keep")
     return keep
+
+
+def tpmcl_limits():
+    """(max tokens, max feature width, max tis_keep tokens) served by csrc/tpmcl.hip, read from the loaded library."""
+    lib = _lib.load()
+    lim = getattr(lib, "antmmf_tpmcl_limits_read", None)   # kept on the handle: one query per loaded library
+    if lim is None:
+        v = [ctypes.c_int(0) for _ in range(3)]
+        _rc(lib.antmmf_tpmcl_limits(*(ctypes.byref(x) for x in v)), "antmmf_tpmcl_limits")
+        lim = lib.antmmf_tpmcl_limits_read = tuple(x.value for x in v)
+    return lim
 
 
 def rank_rows(S, gt_off, gt_idx):

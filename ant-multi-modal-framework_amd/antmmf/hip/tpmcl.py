@@ -7,7 +7,9 @@ What they replace in the reference (prj/dmae_vtp/roi_univl/univl/model/dmae_util
   tis_keep          sort / cumsum / scatter of TokenImportanceSelector (tpmcl_utils.py:101-121); not differentiable (a mask)
   linear_f32        the small fp32 matmuls of the weight predictors (tpmcl_utils.py:35-50), on the bf16 MFMA GEMM via the hi / lo split of
                     contrastive.matmul_f32 (three GEMMs: fp32-accurate products, fp32 accumulation)
-No torch / rocBLAS GEMM, softmax or sort is left on that path.
+No torch / rocBLAS GEMM, softmax or sort is left on that path: every shape either runs on the kernels or raises.  The kernels' limits
+(tokens per item, feature width, tokens per tis_keep row) are read from the loaded library (antmmf_tpmcl_limits); a shape beyond them is a
+ValueError that names the limit.
 """
 import torch
 
@@ -15,7 +17,18 @@ from . import ops
 from .contrastive import matmul_f32      # fp32-accurate products on the bf16 MFMA GEMM (hi / lo split); module-level so that the lane-emulator tests can stub it
 from .functional import GradSink, _note_untracked, f32
 
-TOKEN_WEIGHT_MAX_T, TOKEN_WEIGHT_MAX_D, TIS_KEEP_MAX_T = 128, 1024, 64   # limits of csrc/tpmcl.hip's row kernels
+
+def _check(name, tokens, cols=None):
+    """Raise for a shape outside csrc/tpmcl.hip's served range (cols None: a tis_keep row)."""
+    max_tokens, max_cols, max_keep = ops.tpmcl_limits()
+    if cols is None:
+        if tokens > max_keep:
+            raise ValueError(f"{name}: {tokens} tokens per row, the kernel serves at most {max_keep} (antmmf_tpmcl_limits: max_keep_tokens)")
+        return
+    if tokens > max_tokens:
+        raise ValueError(f"{name}: {tokens} tokens per item, the kernels serve at most {max_tokens} (antmmf_tpmcl_limits: max_tokens)")
+    if cols > max_cols:
+        raise ValueError(f"{name}: feature width {cols}, the kernels serve at most {max_cols} (antmmf_tpmcl_limits: max_cols)")
 
 
 class _TokenWeights(torch.autograd.Function):
@@ -43,15 +56,7 @@ def token_weights(feat, weight, bias=None, mask=None):
     """feat [N, T, D] -> softmax over T of (feat . weight + bias), tokens with mask < 0.5 excluded.  weight: the [1, D] (or [D]) parameter of
     an nn.Linear(D, 1), bias its [1] bias."""
     _note_untracked(weight, bias)
-    if feat.shape[-2] > TOKEN_WEIGHT_MAX_T or feat.shape[-1] > TOKEN_WEIGHT_MAX_D:
-        # beyond the fused kernel's row budget (one workgroup holds a row's T x D features: csrc/tpmcl.hip) -- e.g. frames x patches video tokens: the same
-        # arithmetic as device tensor ops (a shape guard for configurations the shipped ymls do not use, not a second product path)
-        logits = (feat.float() * weight.float().reshape(-1)).sum(-1)
-        if bias is not None:
-            logits = logits + bias.float().reshape(())
-        if mask is not None:
-            logits = logits.masked_fill(mask < 0.5, float("-inf"))
-        return torch.softmax(logits, dim=-1)
+    _check("token_weights", feat.shape[-2], feat.shape[-1])
     return _TokenWeights.apply(feat, weight, bias, mask)
 
 
@@ -73,8 +78,7 @@ class _PairDots(torch.autograd.Function):
 
 def pair_dots(x, y):
     """x [C, D], y [C, V, D] -> [C, V]: x[c] . y[c, v]."""
-    if y.shape[-2] > TOKEN_WEIGHT_MAX_T:   # its backward (pair_wsum / pair_outer) holds the V weights of a pair in one workgroup: same shape guard as token_weights
-        return torch.einsum("cd,cvd->cv", x.float(), y.float())
+    _check("pair_dots", y.shape[-2], y.shape[-1])
     return _PairDots.apply(x, y)
 
 
@@ -96,18 +100,14 @@ class _PairWsum(torch.autograd.Function):
 
 def pair_wsum(w, y):
     """w [C, V], y [C, V, D] -> [C, D]: sum_v w[c, v] y[c, v]."""
-    if y.shape[-2] > TOKEN_WEIGHT_MAX_T:
-        return torch.einsum("cv,cvd->cd", w.float(), y.float())
+    _check("pair_wsum", y.shape[-2], y.shape[-1])
     return _PairWsum.apply(w, y)
 
 
 def tis_keep(weights, thresh):
     """[R, T] token weights -> keep mask (0 = one of the most important tokens whose descending cumulative weight is < thresh)."""
+    _check("tis_keep", weights.shape[-1])
     w = weights.detach().float().contiguous()
-    if w.shape[-1] > TIS_KEEP_MAX_T:   # rows longer than the kernel's 64 lanes: the reference's sort / cumsum / scatter (tpmcl_utils.py:101-121) on the device
-        order = torch.argsort(w, dim=-1, descending=True)
-        drop_sorted = torch.cumsum(torch.gather(w, -1, order), dim=-1) < thresh
-        return 1.0 - torch.zeros_like(w).scatter_(-1, order, drop_sorted.float())
     return ops.tis_keep(w, float(thresh))
 
 
