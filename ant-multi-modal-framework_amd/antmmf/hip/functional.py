@@ -14,7 +14,6 @@ Reference modules replaced by `transformer_layer`:
   "bert"  BertLayer                antmmf/modules/vision/backbone/clip/modeling_bert.py:134-270
   "m2"    torchscale EncoderLayer  prj/M2_Encoder/vlmo/torchscale/architecture/encoder.py:113-168
 """
-import math
 from dataclasses import dataclass
 
 import os
@@ -281,29 +280,24 @@ def l2_normalize(x, eps=1e-12):
 
 class _Attention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, key_bias, heads, scale):
-        o, lse = ops.attention_fwd(q, k, v, heads, scale, key_bias)
+    def forward(ctx, q, k, v, key_bias, heads, scale, dropout_p, seed):
+        o, lse = ops.attention_fwd(q, k, v, heads, scale, key_bias, dropout_p=dropout_p, dropout_seed=seed)
         ctx.save_for_backward(q, k, v, o, lse, key_bias)
-        ctx.heads, ctx.scale = heads, scale
+        ctx.meta = (heads, scale, dropout_p, seed)
         return o
 
     @staticmethod
     def backward(ctx, d_o):
         q, k, v, o, lse, key_bias = ctx.saved_tensors
-        dq, dk, dv = ops.attention_bwd(q, k, v, o, lse, d_o.contiguous(), ctx.heads, ctx.scale, key_bias)
-        return dq, dk, dv, None, None, None
+        heads, scale, dropout_p, seed = ctx.meta
+        dq, dk, dv = ops.attention_bwd(q, k, v, o, lse, d_o.contiguous(), heads, scale, key_bias, dropout_p=dropout_p, dropout_seed=seed)
+        return dq, dk, dv, None, None, None, None, None
 
 
-def attention(q, k, v, heads, scale, key_bias=None):
-    """softmax(scale q k^T + key_bias) v on [B, N, heads*dh] bf16 tensors, head size dh = 64 or 128 (views of a packed projection are fine)."""
-    return _Attention.apply(q, k, v, key_bias, heads, scale)
-
-
-def co_attention(q1, k1, v1, q2, k2, v2, heads, bias1=None, bias2=None):
-    """ViLBERT BertBiAttention core (antmmf/models/vilbert.py:360-400): stream-2 queries attend stream-1
-    keys/values and vice versa; two launches of the same kernel with the streams swapped."""
-    scale = 1.0 / math.sqrt(64)
-    return attention(q2, k1, v1, heads, scale, bias1), attention(q1, k2, v2, heads, scale, bias2)
+def attention(q, k, v, heads, scale, key_bias=None, dropout_p=0.0, seed=0):
+    """softmax(scale q k^T + key_bias) v on [B, N, heads*dh] bf16 tensors, head size dh = 64 or 128 (views of a packed projection are fine).  dropout_p > 0:
+    attention-probability dropout inside the kernel, its counter-based mask of `seed` regenerated in backward."""
+    return _Attention.apply(q, k, v, key_bias, heads, scale, dropout_p, seed)
 
 
 # ------------------------------------------------------------------------------ fused transformer layer
@@ -441,6 +435,41 @@ def _folded_w2(P):
     return _cached_on(P["w2"], "_antmmf_ffn_fold", build)
 
 
+def _layer_attention_fwd(qkv, shape, spec, scale, key_bias, p_att, seed, text):
+    """Self-attention over the layer's packed projection qkv [T, 3d], strided ([B, N] tokens) or token-packed (`text`, a PackedText) -> o (T x d elements), lse."""
+    B, N, d = shape
+    if text is None:
+        q3 = qkv.view(B, N, 3 * d)
+        return ops.attention_fwd(q3[..., :d], q3[..., d:2 * d], q3[..., 2 * d:], spec.heads, scale, key_bias, p_att, seed)
+    o = torch.empty(qkv.shape[0], d, dtype=BF, device=qkv.device)
+    if o.shape[0] > text.total:
+        o[text.total:].zero_()   # the tail rows belong to no item: the kernel leaves them alone, and everything downstream must stay finite (their gradients are exact zeros)
+    return ops.attention_fwd_packed(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], text.items, spec.heads, scale, text.n_max, o=o)
+
+
+def _layer_attention_bwd(qkv, o, lse, do, shape, spec, scale, key_bias, p_att, seed, text, want_sums, sums_v):
+    """Backward of _layer_attention_fwd -> (dQ | dK | dV [T, 3d], tok_sums).  tok_sums ([items, 3d] fp32, or None): the one-kernel backward also returns, per batch
+    item, the token sums of dQ | dK | dV -- their column sums are the q / k / v bias gradients, so the column-sum passes over the B * N rows of dQ | dK | dV (0.19 ms per
+    image-tower layer of the flagship) are not run.  Asked for when the caller has such a bias to fill (`want_sums`) and the library serves the shape."""
+    B, N, d = shape
+    n_items, n_tok = (B, N) if text is None else (text.items.shape[0], text.n_max)
+    dqkv2 = torch.empty(B * N, 3 * d, dtype=BF, device=qkv.device)
+    tok_sums = None
+    # (ATTN_BWD_SUMS_MIN_TOKENS = 129 restricts it to the long towers: the A/B of profiles/r6b_attn_bwd_token_sums_ab.txt -- the short towers gain too, a little)
+    if want_sums and ATTN_BWD_SUMS and n_tok >= ATTN_BWD_SUMS_MIN_TOKENS and ops.attention_bwd_sums_ok(d // spec.heads, n_tok, n_tok, p_att):
+        tok_sums = torch.empty(n_items, 3 * d, dtype=torch.float32, device=qkv.device)
+    if text is None:
+        q3, dq3 = qkv.view(B, N, 3 * d), dqkv2.view(B, N, 3 * d)
+        ops.attention_bwd(q3[..., :d], q3[..., d:2 * d], q3[..., 2 * d:], o, lse, do.view(B, N, d), spec.heads, scale, key_bias,
+                          dq=dq3[..., :d], dk=dq3[..., d:2 * d], dv=dq3[..., 2 * d:], dropout_p=p_att, dropout_seed=seed, sums=tok_sums, sums_v=sums_v)
+    else:
+        if B * N > text.total:
+            dqkv2[text.total:].zero_()   # rows of no item: not written by the kernel, read by the wgrads and the dgrad of the caller
+        ops.attention_bwd_packed(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], text.items, o, lse, do, spec.heads, scale, text.n_max,
+                                 dqkv2[:, :d], dqkv2[:, d:2 * d], dqkv2[:, 2 * d:], sums=tok_sums, sums_v=sums_v)
+    return dqkv2, tok_sums
+
+
 class _TransformerLayer(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, key_bias, spec, seed, text, *params):
@@ -470,15 +499,9 @@ class _TransformerLayer(torch.autograd.Function):
             h = x2
         qkv = ops.gemm(h, wqkv, bias=bqkv)  # [T, 3d]
         del h
-        q3 = qkv.view(B, N, 3 * d)
-        if text is not None:
-            o = torch.empty(T, d, dtype=BF, device=dev)
-            if T > text.total:
-                o[text.total:].zero_()   # the tail rows belong to no item: the kernel leaves them alone, and everything downstream must stay finite (their gradients are exact zeros)
-            o, lse = ops.attention_fwd_packed(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], text.items, spec.heads, scale, text.n_max, o=o)
-        else:
-            o, lse = ops.attention_fwd(q3[..., :d], q3[..., d:2 * d], q3[..., 2 * d:], spec.heads, scale, key_bias, p_att, seed)
+        o, lse = _layer_attention_fwd(qkv, (B, N, d), spec, scale, key_bias, p_att, seed, text)
         if KEY_IMPORTANCE is not None:   # `output_attentions=True` callers: the head-mean column sums of this layer's probabilities join the collector
+            q3 = qkv.view(B, N, 3 * d)
             ops.attention_key_importance_(KEY_IMPORTANCE, q3[..., :d], q3[..., d:2 * d], lse, spec.heads, scale, key_bias, p_att, seed or 0, weight=1.0 / spec.heads)
         o2 = o.view(T, d)
         st_in = None
@@ -687,28 +710,10 @@ class _TransformerLayer(torch.autograd.Function):
             _bgrad(sink, P["bo"], dy_wo)
         del o_n
         text = ctx.text
-        q3 = qkv.view(B, N, 3 * d)
-        dqkv = torch.empty(B, N, 3 * d, dtype=BF, device=qkv.device)
-        n_items, n_tok = (B, N) if text is None else (text.items.shape[0], text.n_max)
-        # q / k / v bias gradients: the one-kernel attention backward also returns, per batch item, the token sums of dQ | dK | dV ([B, 3d] fp32) -- their column
-        # sums are the bias gradients, so the column-sum passes over the B * N rows of dQ | dK | dV (0.19 ms per image-tower layer of the flagship) are not run
         qkv_biases = [P["bqkv"]] if spec.packed_qkv else [P["bq"], P["bk"], P["bv"]]
-        tok_sums = None
-        # (ATTN_BWD_SUMS_MIN_TOKENS = 129 restricts it to the long towers: the A/B of profiles/r6b_attn_bwd_token_sums_ab.txt -- the short towers gain too, a little)
-        if (ATTN_BWD_SUMS and n_tok >= ATTN_BWD_SUMS_MIN_TOKENS and d == 64 * spec.heads and any(b_ is not None and b_.requires_grad for b_ in qkv_biases)
-                and ops.attention_bwd_sums_ok(64, n_tok, n_tok, p_att)):
-            tok_sums = torch.empty(n_items, 3 * d, dtype=torch.float32, device=qkv.device)
-        if text is not None:
-            dq2 = dqkv.view(T, 3 * d)
-            if T > text.total:
-                dq2[text.total:].zero_()   # rows of no item: not written by the kernel, read by the wgrads and the dgrad below
-            ops.attention_bwd_packed(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], text.items, o, lse, do, spec.heads, scale, text.n_max,
-                                     dq2[:, :d], dq2[:, d:2 * d], dq2[:, 2 * d:], sums=tok_sums, sums_v=not bv_fused)
-        else:
-            ops.attention_bwd(q3[..., :d], q3[..., d:2 * d], q3[..., 2 * d:], o, lse, do.view(B, N, d), spec.heads, scale, key_bias,
-                              dq=dqkv[..., :d], dk=dqkv[..., d:2 * d], dv=dqkv[..., 2 * d:], dropout_p=p_att, dropout_seed=seed, sums=tok_sums, sums_v=not bv_fused)
+        dqkv2, tok_sums = _layer_attention_bwd(qkv, o, lse, do, (B, N, d), spec, scale, key_bias, p_att, seed, text,
+                                               want_sums=any(b_ is not None and b_.requires_grad for b_ in qkv_biases), sums_v=not bv_fused)
         del do
-        dqkv2 = dqkv.view(T, 3 * d)
         bsrc = tok_sums if tok_sums is not None else dqkv2   # what the q / k / v bias gradients are column sums of
         dx = None
         if pre_ln:   # (also when x itself needs no gradient: ln1's own parameters do)

@@ -594,39 +594,53 @@ def attention_key_importance_(out, q, k, lse, heads, scale, key_bias=None, dropo
 
 
 def attention_bwd_sums_ok(head_dim, Nq, Nk, dropout_p=0.0):
-    """True when attention_bwd(..., sums=...) is served: the one-kernel backward's shapes (head size 64, no dropout, 33 ... 272 keys)."""
+    """True when attention_bwd(..., sums=...) is served: the one-kernel backward's shapes (today head size 64, no dropout, 33 ... 272 keys; the library decides)."""
     return bool(_lib.load().antmmf_attention_bwd_sums_ok(int(head_dim), int(Nq), int(Nk), float(dropout_p)))
+
+
+def _attention_bwd(name, q, k, v, o, lse, d_o, heads, scale, dq, dk, dv, key_bias=None, items=None, n_max=None, dropout_p=0.0, dropout_seed=0, sums=None, sums_v=True):
+    """The one backward behind attention_bwd ([B, N, D] operands) and attention_bwd_packed (`items`: [T, D] operands): validation, then the one of the four entry
+    points (plain | sums) x (strided | packed) that takes the arguments.  What is not served comes back as the library's ANTMMF_EINVAL."""
+    packed = items is not None
+    _dev_ok(q, k, v, items, o, lse, d_o, key_bias, dq, dk, dv, sums)
+    _c(o, "o"); _c(d_o, "d_o")
+    D = q.shape[-1]
+    dh = _head_dim(D, heads)
+    if packed:
+        _items_ok(items); _c(lse, "lse")
+        B, Nq, Nk, ld = items.shape[0], int(n_max), int(n_max), _row_ld
+        if tuple(lse.shape) != (B, heads, Nq):
+            raise ValueError(f"{name}: lse must be [B, heads, n_max]")
+    else:
+        B, Nq, Nk, ld = q.shape[0], q.shape[1], k.shape[1], _tok_ld
+    if (packed or sums is not None) and (dh != 64 or dropout_p):   # (their entry points take neither argument; every other limit is the library's to report)
+        raise ValueError(f"{name}: the packed form and the token sums exist for head size 64 without dropout only")
+    sum_args = ()
+    if sums is not None:
+        _c(sums, "sums"); _f32(sums, "sums")
+        if tuple(sums.shape) != (B, 3 * D):
+            raise ValueError(f"{name}: sums must be [B, 3 * D] fp32")
+        sum_args = (_p(sums), 1 if sums_v else 0)
+    ptrs = (_p(q), _p(k), _p(v), _p(items) if packed else _p(key_bias), _p(o), _p(lse), _p(d_o), _p(dq), _p(dk), _p(dv))
+    tail = (ld(q, "q"), ld(k, "k"), ld(v, "v"), D, D, ld(dq, "dq"), ld(dk, "dk"), ld(dv, "dv"), float(scale))
+    entry, args = {
+        (False, False): ("antmmf_attention_bwd_hd", (*ptrs, B, heads, dh, Nq, Nk, *tail, float(dropout_p), int(dropout_seed))),
+        (False, True): ("antmmf_attention_bwd_sums", (*ptrs, *sum_args, B, heads, Nq, Nk, *tail)),
+        (True, False): ("antmmf_attention_bwd_packed", (*ptrs, B, heads, Nq, *tail)),
+        (True, True): ("antmmf_attention_bwd_sums_packed", (*ptrs, *sum_args, B, heads, Nq, *tail)),
+    }[packed, sums is not None]
+    _rc(getattr(_lib.load(), entry)(*args, _stream()), entry)
+    return dq, dk, dv
 
 
 def attention_bwd(q, k, v, o, lse, d_o, heads, scale, key_bias=None, dq=None, dk=None, dv=None, dropout_p=0.0, dropout_seed=0, sums=None, sums_v=True):
     """`sums` [B, 3 * D] fp32 (contiguous): also filled with the per-batch-item token sums of dQ | dK | dV -- the q / k / v bias gradients are its column sums
     (check attention_bwd_sums_ok first: only the one-kernel backward's shapes are served); sums_v=False leaves the dV third unwritten."""
-    _dev_ok(q, k, v, o, lse, d_o, key_bias, dq, dk, dv, sums)
-    B, Nq, D = q.shape
-    Nk = k.shape[1]
-    dh = _head_dim(D, heads)
-    _c(o, "o"); _c(d_o, "d_o")
-    if dq is None:
-        dq = torch.empty(B, Nq, D, dtype=torch.bfloat16, device=q.device)
-    if dk is None:
-        dk = torch.empty(B, Nk, D, dtype=torch.bfloat16, device=q.device)
-    if dv is None:
-        dv = torch.empty(B, Nk, D, dtype=torch.bfloat16, device=q.device)
-    if sums is not None:
-        _c(sums, "sums"); _f32(sums, "sums")
-        if tuple(sums.shape) != (B, 3 * D) or dh != 64 or dropout_p:
-            raise ValueError("attention_bwd: sums must be [B, 3 * D] fp32 with head size 64 and no dropout")
-        _rc(_lib.load().antmmf_attention_bwd_sums(_p(q), _p(k), _p(v), _p(key_bias), _p(o), _p(lse), _p(d_o), _p(dq), _p(dk), _p(dv), _p(sums),
-                                                  1 if sums_v else 0, B, heads, Nq, Nk, _tok_ld(q, "q"), _tok_ld(k, "k"), _tok_ld(v, "v"), D, D,
-                                                  _tok_ld(dq, "dq"), _tok_ld(dk, "dk"), _tok_ld(dv, "dv"), float(scale), _stream()),
-            "antmmf_attention_bwd_sums")
-        return dq, dk, dv
-    _rc(_lib.load().antmmf_attention_bwd_hd(_p(q), _p(k), _p(v), _p(key_bias), _p(o), _p(lse), _p(d_o), _p(dq), _p(dk), _p(dv),
-                                            B, heads, dh, Nq, Nk, _tok_ld(q, "q"), _tok_ld(k, "k"), _tok_ld(v, "v"), D, D,
-                                            _tok_ld(dq, "dq"), _tok_ld(dk, "dk"), _tok_ld(dv, "dv"), float(scale), float(dropout_p),
-                                            int(dropout_seed), _stream()),
-        "antmmf_attention_bwd_hd")
-    return dq, dk, dv
+    def out(t, like):
+        return torch.empty(q.shape[0], like.shape[1], q.shape[2], dtype=torch.bfloat16, device=q.device) if t is None else t
+
+    return _attention_bwd("attention_bwd", q, k, v, o, lse, d_o, heads, scale, out(dq, q), out(dk, k), out(dv, k), key_bias=key_bias,
+                          dropout_p=dropout_p, dropout_seed=dropout_seed, sums=sums, sums_v=sums_v)
 
 
 # ------------------------------------------------------------------------------ token-packed self-attention / embedding (the M2 text tower without its padding)
@@ -643,7 +657,7 @@ def _items_ok(items, name="items"):
 
 
 def attention_packed_ok(head_dim, n_max):
-    """True when the packed entry points serve items of up to n_max tokens (head size 64, 33 ... 128)."""
+    """True when the packed entry points serve items of up to n_max tokens (today head size 64, 33 ... 128; the library decides)."""
     return bool(_lib.load().antmmf_attention_packed_ok(int(head_dim), int(n_max)))
 
 
@@ -653,7 +667,7 @@ def attention_fwd_packed(q, k, v, items, heads, scale, n_max, o=None):
     _dev_ok(q, k, v, items, o); _items_ok(items)
     T, D = q.shape
     B = items.shape[0]
-    if _head_dim(D, heads) != 64:
+    if _head_dim(D, heads) != 64:   # (the entry point takes no head size; every other limit is the library's to report)
         raise ValueError("attention_fwd_packed: head size 64 only")
     if o is None:
         o = torch.empty(T, D, dtype=torch.bfloat16, device=q.device)
@@ -666,24 +680,7 @@ def attention_fwd_packed(q, k, v, items, heads, scale, n_max, o=None):
 
 def attention_bwd_packed(q, k, v, items, o, lse, d_o, heads, scale, n_max, dq, dk, dv, sums=None, sums_v=True):
     """Backward of attention_fwd_packed into dq | dk | dv [T, D] (given: rows of no item are not written); sums [B, 3 * D] fp32 as in attention_bwd."""
-    _dev_ok(q, k, v, items, o, lse, d_o, dq, dk, dv, sums); _items_ok(items)
-    T, D = q.shape
-    B = items.shape[0]
-    _c(o, "o"); _c(d_o, "d_o"); _c(lse, "lse")
-    if _head_dim(D, heads) != 64 or tuple(lse.shape) != (B, heads, n_max):
-        raise ValueError("attention_bwd_packed: head size 64 and lse [B, heads, n_max]")
-    lds = (_row_ld(q, "q"), _row_ld(k, "k"), _row_ld(v, "v"), D, D, _row_ld(dq, "dq"), _row_ld(dk, "dk"), _row_ld(dv, "dv"))
-    if sums is not None:
-        _c(sums, "sums"); _f32(sums, "sums")
-        if tuple(sums.shape) != (B, 3 * D):
-            raise ValueError("attention_bwd_packed: sums must be [B, 3 * D] fp32")
-        _rc(_lib.load().antmmf_attention_bwd_sums_packed(_p(q), _p(k), _p(v), _p(items), _p(o), _p(lse), _p(d_o), _p(dq), _p(dk), _p(dv), _p(sums),
-                                                         1 if sums_v else 0, B, heads, int(n_max), *lds, float(scale), _stream()),
-            "antmmf_attention_bwd_sums_packed")
-    else:
-        _rc(_lib.load().antmmf_attention_bwd_packed(_p(q), _p(k), _p(v), _p(items), _p(o), _p(lse), _p(d_o), _p(dq), _p(dk), _p(dv), B, heads, int(n_max),
-                                                    *lds, float(scale), _stream()), "antmmf_attention_bwd_packed")
-    return dq, dk, dv
+    return _attention_bwd("attention_bwd_packed", q, k, v, o, lse, d_o, heads, scale, dq, dk, dv, items=items, n_max=n_max, sums=sums, sums_v=sums_v)
 
 
 def embed_gather_packed(ids, word, pos, items, out, pos_offset=0):

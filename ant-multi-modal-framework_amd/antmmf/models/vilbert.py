@@ -18,25 +18,6 @@ import torch
 from torch import nn
 
 from antmmf.hip import functional as HF
-from antmmf.hip import ops
-
-
-class _AttentionDrop(torch.autograd.Function):
-    """Fused attention with attention-probability dropout (counter-based mask regenerated in backward)."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, key_bias, heads, scale, p, seed):
-        o, lse = ops.attention_fwd(q, k, v, heads, scale, key_bias, dropout_p=p, dropout_seed=seed)
-        ctx.save_for_backward(q, k, v, o, lse, key_bias)
-        ctx.meta = (heads, scale, p, seed)
-        return o
-
-    @staticmethod
-    def backward(ctx, d_o):
-        q, k, v, o, lse, key_bias = ctx.saved_tensors
-        heads, scale, p, seed = ctx.meta
-        dq, dk, dv = ops.attention_bwd(q, k, v, o, lse, d_o.contiguous(), heads, scale, key_bias, dropout_p=p, dropout_seed=seed)
-        return dq, dk, dv, None, None, None, None, None
 
 
 class BertBiAttention(nn.Module):
@@ -95,6 +76,6 @@ class BertBiAttention(nn.Module):
         s1, s2 = dropout_seeds if dropout_seeds is not None else (0, 0)
         h = self.num_attention_heads
         # context 1: text queries over vision keys / values (reference :357-376); context 2: vision queries over text (:378-401)
-        ctx1 = _AttentionDrop.apply(q2, k1, v1, b1, h, scale, p1, s1) if p1 > 0 else HF.attention(q2, k1, v1, h, scale, b1)
-        ctx2 = _AttentionDrop.apply(q1, k2, v2, b2, h, scale, p2, s2) if p2 > 0 else HF.attention(q1, k2, v2, h, scale, b2)
+        ctx1 = HF.attention(q2, k1, v1, h, scale, b1, p1, s1)
+        ctx2 = HF.attention(q1, k2, v2, h, scale, b2, p2, s2)
         return ctx1, ctx2, None

@@ -904,13 +904,6 @@ static inline size_t attn_fused_lds_bytes(int Nq, int Nk, bool early = false, bo
     const int nqp = ((Nq + 31) / 32) * 32;
     return (size_t)nqp * 256 * (early ? 2 : 1) + 288 * 128 + 2 * 16384 + (Nk > 256 ? (size_t)(nqp / 32) * 1024 : 0) + (size_t)nqp * 8 + (sums ? ATTN_SUMS_FLOATS * 4 : 0);
 }
-static inline bool attn_fused_ok(const AttnArgs& a) {
-    // (every shape of the one-kernel backward is served.  With the per-chunk dQ sums in LDS the sums cost ~ 1 us per (b, h) item -- 15 % of the 77 - 86-token forms, more than the
-    // column-sum pass they save -- and the short towers were excluded; with the dQ tiles summed in registers it is 0.025 ms of 0.41 at 1024 x 16 x 77 against a pass of 0.055:
-    // profiles/r6b_attn_bwd_token_sums_ab.txt)
-    if (a.sums && a.Nk <= ATTN_SUMS_MIN_KEYS) return false;
-    return !a.drop_thr && a.Nk > 32 && a.Nk <= 272 && attn_fused_lds_bytes(a.Nq, a.Nk, false, a.sums != nullptr) <= 160 * 1024;   // (one or two key tiles: the two-kernel form)
-}
 
 // one score block: 16 queries (tile at q0) x the 16 keys of (kf, vf): p = softmax probabilities, ds = p * (dP - D).  Lane: key l15, queries q0 + 4 grp + r.
 #define FUSED_SCORE_BLOCK(KF, VF, KBIAS, P, DSV)                                                              \
@@ -1450,193 +1443,212 @@ __global__ __launch_bounds__(ATTN_THREADS, 1) void attn_bwd_fused64_kernel(const
 #undef ITNK
 
 // ---- C ABI --------------------------------------------------------------------------------------------
-static bool attn_args_ok(const AttnArgs& a, int dh) {
-    return (dh == 64 || dh == 128) && a.B > 0 && a.heads > 0 && a.Nq > 0 && a.Nk > 0 && a.Nk <= 288 && a.Nq <= 288 && !(a.ldq & 7) && !(a.ldk & 7) &&
-           !(a.ldv & 7) && !(a.ldo & 3);
-}
+// Which kernel form serves a shape -- and whether it is served at all -- is decided HERE, once: the launchers switch on the plan, the "is it served" queries and the
+// entry points' refusals are calls of the same two functions.  Plain integers in, no HIP call.
 template <typename K>
 static void set_lds(K kern, size_t bytes) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); }
+#define ATTN_LAUNCH(KERN, GRID, LDS, STREAM, ...) do { set_lds(KERN, LDS); hipLaunchKernelGGL(KERN, dim3(GRID), dim3(ATTN_THREADS), LDS, STREAM, __VA_ARGS__); } while (0)
+#define ATTN_BWDF(P, A, STREAM, NKS, HASE, FULL, NQC, PERS, ABL, EARLY, SUMS)   /* the one-kernel backward of plan P */ \
+    ATTN_LAUNCH((attn_bwd_fused64_kernel<NKS, HASE, FULL, NQC, PERS, ABL, EARLY, SUMS>), (P).grid, (P).lds, STREAM, A, (P).nqp, (A).B * (A).heads)
 
-template <int DH>
-static int attn_fwd_launch(const AttnArgs& a, hipStream_t stream) {
-    const int nch = (a.Nk + 31) / 32;
-    const dim3 grid((unsigned)(a.B * a.heads)), block(ATTN_THREADS);
-#define FWD(N) do { const size_t lds = (size_t)(32 * N) * (4 * DH) + (32 * N) * 4; \
-        if (a.drop_thr) { set_lds(attn_fwd_kernel<N, true, DH>, lds); hipLaunchKernelGGL((attn_fwd_kernel<N, true, DH>), grid, block, lds, stream, a); } \
-        else { set_lds(attn_fwd_kernel<N, false, DH>, lds); hipLaunchKernelGGL((attn_fwd_kernel<N, false, DH>), grid, block, lds, stream, a); } } while (0)
-    // attn_fwd32_kernel (32 x 32 x 16 tiles, online softmax) is an OPT-IN experiment: ANTMMF_ATTN_VARIANT bit 2 selects it for the long rows without dropout, bit 1 its
-    // 64-key softmax blocks.  Measured same-box against the 16 x 16 whole-row kernel at 1024 x 16 heads x 257 tokens (profiles/r4_attn_fwd32_ab.txt): 0.78 - 0.81 ms vs
-    // 0.72 - 0.73 ms -- half the LDS instructions and bytes, fewer parked cycles (34 % vs 48 %), but more issue stalls behind the 16-pass MFMAs (35 % vs 24 %) and the same
-    // VALU work per score (one 16-cycle v_exp_f32 per score is as long as all the MFMAs of a tile): not faster, so not the default.
-#ifdef ANTMMF_LAB
-    static const char* av_env = ANTMMF_LAB_ENV("ANTMMF_ATTN_VARIANT");
-    const int av = av_env ? atoi(av_env) : 0;
-    if constexpr (DH == 64) {
-        if (!a.drop_thr && !a.items && (nch == 7 || nch == 9) && (av & 4)) {   // (its padding mask covers the LAST 32-key tile only: the key count must fill the instantiated tile count)
-#define FWD32K(N, HB, KB) do { const size_t lds = (size_t)(32 * N) * 256 + (32 * N) * 4 + 8 * 2 * 68 * 4; set_lds(attn_fwd32_kernel<N, HB, KB>, lds); \
-            hipLaunchKernelGGL((attn_fwd32_kernel<N, HB, KB>), grid, block, lds, stream, a); } while (0)
-#define FWD32(N, HB) do { if (av & 2) FWD32K(N, HB, 2); else FWD32K(N, HB, 1); } while (0)   /* variant bit 1: 64-key softmax blocks */
-            if (nch == 7) { if (a.key_bias) FWD32(7, true); else FWD32(7, false); }
-            else { if (a.key_bias) FWD32(9, true); else FWD32(9, false); }
-#undef FWD32
-#undef FWD32K
-            return antmmf_check_launch();
-        }
+static bool attn_shape_ok(int dh, int B, int heads, int Nq, int Nk) { return (dh == 64 || dh == 128) && B > 0 && heads > 0 && Nq > 0 && Nk > 0 && Nq <= 288 && Nk <= 288; }
+// 32-key chunks the whole-row kernels (forward, the two-kernel backward's dQ kernel) are instantiated for
+static int attn_key_chunks(int Nk) { const int nch = (Nk + 31) / 32; return nch <= 1 ? 1 : nch <= 3 ? 3 : nch <= 7 ? 7 : 9; }
+// forward: the NCH of attn_fwd_kernel, 0 = not served (the packed form: head size 64)
+static int attn_fwd_plan(int dh, int B, int heads, int Nq, int Nk, bool packed) { return attn_shape_ok(dh, B, heads, Nq, Nk) && !(packed && dh != 64) ? attn_key_chunks(Nk) : 0; }
+
+enum AttnBwdForm { ATTN_BWD_NONE = 0 /* ANTMMF_EINVAL */, ATTN_BWD_TWO_KERNEL, ATTN_BWD_FUSED_PER_ITEM, ATTN_BWD_FUSED_PERSIST };
+struct AttnBwdPlan {
+    AttnBwdForm form;
+    int nch;                   // two kernels: NCH of the dQ kernel
+    int nks; bool hase, full;  // one kernel: NKS, HASE, FULL of attn_bwd_fused64_kernel (its NQC is 9 in the persistent form with the 17th key tile, else 0)
+    bool early;                // one kernel: the double-buffered persistent form (the only one that reads an item table)
+    int nqp;                   // queries padded to 32
+    size_t lds;                // of the fused kernel / of the dQ kernel
+    unsigned grid;
+};
+// the two-kernel form of any served shape (what the plan falls back to, and what the lab library's A/B switch forces)
+static void attn_bwd_two_kernel(AttnBwdPlan& p, int dh, int B, int heads, int Nk) {
+    p.form = ATTN_BWD_TWO_KERNEL; p.nch = attn_key_chunks(Nk); p.lds = (size_t)(32 * p.nch) * (4 * dh + 4); p.grid = (unsigned)(B * heads);
+}
+// sums: 0 none, 1 dQ | dK | dV, 2 dQ | dK.  persist_wgs: workgroups of the persistent form (one per CU walking the items)
+static AttnBwdPlan attn_bwd_plan(int dh, int B, int heads, int Nq, int Nk, bool dropout, bool packed, int sums, unsigned persist_wgs) {
+    AttnBwdPlan p{};
+    if (!attn_shape_ok(dh, B, heads, Nq, Nk)) return p;
+    const size_t lds_max = 160 * 1024;
+    const unsigned n_items = (unsigned)(B * heads);
+    p.nqp = ((Nq + 31) / 32) * 32;
+    // One kernel: head size 64, no dropout, 33 ... 272 keys (one or two key tiles: the two-kernel form).  Every such shape is served with the token sums too: with the
+    // per-chunk dQ sums in LDS they cost ~ 1 us per (b, h) item -- 15 % of the 77 - 86-token forms, more than the column-sum pass they save -- and the short towers were
+    // excluded; with the dQ tiles summed in registers it is 0.025 ms of 0.41 at 1024 x 16 x 77 against a pass of 0.055: profiles/r6b_attn_bwd_token_sums_ab.txt
+    const bool fused = dh == 64 && !dropout && Nk > 32 && Nk <= 272 && !(sums && Nk <= ATTN_SUMS_MIN_KEYS) && attn_fused_lds_bytes(Nq, Nk, false, sums != 0) <= lds_max;
+    if (!fused) {
+        if (sums || packed) return p;   // (neither exists in the two-kernel form)
+        attn_bwd_two_kernel(p, dh, B, heads, Nk);
+        return p;
     }
-#endif
+    const int nkt = (Nk + 15) / 16;
+    // all sixteen resident key tiles present (the 197- / 257-token towers): the persistent form.  A 17th key tile with other query counts: run-time chunk loops, spills there
+    const bool persist = nkt <= 16 || p.nqp == 288;
+    p.early = persist && nkt <= 8 && attn_fused_lds_bytes(Nq, Nk, true, sums != 0) <= lds_max;
+    if (packed && !p.early) return p;   // (the item table is read by the double-buffered persistent forms only -- ITQ0 ... ITNK)
+    p.form = persist ? ATTN_BWD_FUSED_PERSIST : ATTN_BWD_FUSED_PER_ITEM;
+    p.lds = attn_fused_lds_bytes(Nq, Nk, p.early, sums != 0);
+    p.grid = persist && persist_wgs < n_items ? persist_wgs : n_items;
+    p.nks = nkt >= 16 ? 8 : (nkt + 1) / 2;                  // resident key-tile pairs
+    p.hase = nkt > 16;                                      // the 17th key tile
+    p.full = nkt >= 16;
+    return p;
+}
+
 #ifdef ANTMMF_LAB
+// The lab library's switches (same-box A/Bs, timing-only ablations with wrong results, small grids for the tests): read once, applied by ONE function per launcher
+static long g_attn_fused_launches = 0;   // backward calls served by the one-kernel path (tests: "that kernel really ran")
+extern "C" long antmmf_debug_attn_fused_launches() { return g_attn_fused_launches; }
+struct AttnLabEnv { int variant, fwd_abl, fwd_stagger, persist_wgs, fused_abl, sums_abl; };
+static const AttnLabEnv& attn_lab_env() {
+    auto num = [](const char* name, int unset) { const char* s = ANTMMF_LAB_ENV(name); return s ? atoi(s) : unset; };
+    static const AttnLabEnv e = {num("ANTMMF_ATTN_VARIANT", 0), num("ANTMMF_ATTN_FWD_ABL", 0), num("ANTMMF_ATTN_FWD_STAGGER", 0), num("ANTMMF_ATTN_PERSIST_WGS", 256),
+                                 num("ANTMMF_ATTN_FUSED_ABL", 0), num("ANTMMF_ATTN_SUMS_ABL", 0)};
+    return e;
+}
+// Forward.  attn_fwd32_kernel (32 x 32 x 16 tiles, online softmax) is an OPT-IN experiment: ANTMMF_ATTN_VARIANT bit 2 selects it for the long rows without dropout, bit 1 its
+// 64-key softmax blocks.  Measured same-box against the 16 x 16 whole-row kernel at 1024 x 16 heads x 257 tokens (profiles/r4_attn_fwd32_ab.txt): 0.78 - 0.81 ms vs
+// 0.72 - 0.73 ms -- half the LDS instructions and bytes, fewer parked cycles (34 % vs 48 %), but more issue stalls behind the 16-pass MFMAs (35 % vs 24 %) and the same
+// VALU work per score (one 16-cycle v_exp_f32 per score is as long as all the MFMAs of a tile): not faster, so not the default.
+// ANTMMF_ATTN_FWD_ABL: timing-only ablations of the 257-token forward.  Returns true when it launched in place of the plan's kernel.
+template <int DH>
+static bool attn_fwd_lab(AttnArgs& a, hipStream_t stream) {
+    const AttnLabEnv& e = attn_lab_env();
+    if (!a.items) a.fwd_stagger = e.fwd_stagger;
     if constexpr (DH == 64) {
-        static const char* fa_env = ANTMMF_LAB_ENV("ANTMMF_ATTN_FWD_ABL");   // timing-only ablations of the 257-token forward (wrong results)
-        const int fa = fa_env ? atoi(fa_env) : 0;
-        if (fa && nch == 9 && !a.drop_thr && !a.items) {
-            const size_t lds = (size_t)(32 * 9) * (4 * DH) + (32 * 9) * 4;
-#define FWDA(A) case A: set_lds(attn_fwd_kernel<9, false, 64, A>, lds); hipLaunchKernelGGL((attn_fwd_kernel<9, false, 64, A>), grid, block, lds, stream, a); return antmmf_check_launch();
-            switch (fa) { FWDA(1) FWDA(2) FWDA(4) FWDA(8) FWDA(16) FWDA(32) FWDA(24) FWDA(25) FWDA(38) FWDA(63) FWDA(27) default: break; }
+        const int nch = (a.Nk + 31) / 32, grid = a.B * a.heads;
+        if (a.drop_thr || a.items) return false;
+        if ((e.variant & 4) && (nch == 7 || nch == 9)) {   // (its padding mask covers the LAST 32-key tile only: the key count must fill the instantiated tile count)
+#define FWD32(N, HB, KB) ATTN_LAUNCH((attn_fwd32_kernel<N, HB, KB>), grid, (size_t)(32 * N) * 256 + (32 * N) * 4 + 8 * 2 * 68 * 4, stream, a)
+            switch ((nch == 9 ? 4 : 0) | (a.key_bias ? 2 : 0) | ((e.variant & 2) ? 1 : 0)) {   // variant bit 1: 64-key softmax blocks
+                case 0: FWD32(7, false, 1); break; case 1: FWD32(7, false, 2); break; case 2: FWD32(7, true, 1); break; case 3: FWD32(7, true, 2); break;
+                case 4: FWD32(9, false, 1); break; case 5: FWD32(9, false, 2); break; case 6: FWD32(9, true, 1); break; default: FWD32(9, true, 2); break;
+            }
+#undef FWD32
+            return true;
+        }
+        if (nch == 9) {
+#define FWDA(A) case A: ATTN_LAUNCH((attn_fwd_kernel<9, false, 64, A>), grid, (size_t)(32 * 9) * (4 * 64) + (32 * 9) * 4, stream, a); return true;
+            switch (e.fwd_abl) { FWDA(1) FWDA(2) FWDA(4) FWDA(8) FWDA(16) FWDA(32) FWDA(24) FWDA(25) FWDA(38) FWDA(63) FWDA(27) default: break; }
 #undef FWDA
         }
     }
+    return false;
+}
+// Backward: ANTMMF_ATTN_VARIANT bit 3 = the two-kernel form everywhere (same-box A/B), ANTMMF_ATTN_PERSIST_WGS = the persistent grid (a small one makes every workgroup
+// walk several items), ANTMMF_ATTN_FUSED_ABL / ANTMMF_ATTN_SUMS_ABL = timing-only ablations of the 257-token form.  Returns true when it launched in place of the plan's kernel.
+static bool attn_bwd_lab(AttnBwdPlan& p, int dh, const AttnArgs& a, int sums, hipStream_t stream) {
+    const AttnLabEnv& e = attn_lab_env();
+    if (p.form != ATTN_BWD_FUSED_PER_ITEM && p.form != ATTN_BWD_FUSED_PERSIST) return false;
+    if ((e.variant & 8) && !sums && !a.items) { attn_bwd_two_kernel(p, dh, a.B, a.heads, a.Nk); return false; }
+    ++g_attn_fused_launches;
+    if (p.form != ATTN_BWD_FUSED_PERSIST) return false;
+    const unsigned n_items = (unsigned)(a.B * a.heads);
+    p.grid = (unsigned)e.persist_wgs < n_items ? (unsigned)e.persist_wgs : n_items;
+    if (!p.hase) return false;
+#define BWDA(A) case A: ATTN_BWDF(p, a, stream, 8, true, true, 9, true, A, false, 0); return true;
+#define BWDS(A) case A: ATTN_BWDF(p, a, stream, 8, true, true, 9, true, 0, false, 2 | A); return true;   /* 16 no per-chunk dQ sums, 32 no end-of-item partials, 64 no finalisation */
+    if (sums) switch (e.sums_abl) { BWDS(16) BWDS(32) BWDS(64) BWDS(48) BWDS(112) default: break; }
+    else switch (e.fused_abl) { BWDA(1) BWDA(2) BWDA(4) BWDA(8) BWDA(16) BWDA(32) BWDA(15) BWDA(128) BWDA(256) default: break; }
+#undef BWDS
+#undef BWDA
+    return false;
+}
 #endif
-    if (nch <= 1) FWD(1); else if (nch <= 3) FWD(3); else if (nch <= 7) FWD(7); else FWD(9);
+
+template <int DH>
+static int attn_fwd_launch(AttnArgs a, hipStream_t stream) {
+    const int nch = attn_fwd_plan(DH, a.B, a.heads, a.Nq, a.Nk, a.items != nullptr);
+#ifdef ANTMMF_LAB
+    if (nch && attn_fwd_lab<DH>(a, stream)) return antmmf_check_launch();
+#endif
+#define FWD(N) do { const size_t lds = (size_t)(32 * N) * (4 * DH) + (32 * N) * 4; \
+        if (a.drop_thr) ATTN_LAUNCH((attn_fwd_kernel<N, true, DH>), a.B * a.heads, lds, stream, a); else ATTN_LAUNCH((attn_fwd_kernel<N, false, DH>), a.B * a.heads, lds, stream, a); } while (0)
+    switch (nch) { case 1: FWD(1); break; case 3: FWD(3); break; case 7: FWD(7); break; case 9: FWD(9); break; default: return ANTMMF_EINVAL; }
 #undef FWD
     return antmmf_check_launch();
 }
 
-#ifdef ANTMMF_LAB
-static long g_attn_fused_launches = 0;   // backward calls served by the one-kernel path (tests: "that kernel really ran")
-extern "C" long antmmf_debug_attn_fused_launches() { return g_attn_fused_launches; }
-#endif
 template <int DH>
 static int attn_bwd_launch(const AttnArgs& a, hipStream_t stream) {
-    const int nch = (a.Nk + 31) / 32;
-    const dim3 grid((unsigned)(a.B * a.heads)), block(ATTN_THREADS);
+    const int sums = a.sums ? (a.sums_v ? 1 : 2) : 0;
+    AttnBwdPlan p = attn_bwd_plan(DH, a.B, a.heads, a.Nq, a.Nk, a.drop_thr != 0, a.items != nullptr, sums, 256u);
+#ifdef ANTMMF_LAB
+    if (attn_bwd_lab(p, DH, a, sums, stream)) return antmmf_check_launch();
+#endif
+    if (p.form == ATTN_BWD_NONE) return ANTMMF_EINVAL;
     if constexpr (DH == 64) {
-        bool fused = attn_fused_ok(a);
-#ifdef ANTMMF_LAB
-        static const char* bv_env = ANTMMF_LAB_ENV("ANTMMF_ATTN_VARIANT");   // bit 3: the two-kernel backward everywhere (same-box A/B)
-        if (bv_env && (atoi(bv_env) & 8) && !a.sums && !a.items) fused = false;
-#endif
-        if (fused) {
-#ifdef ANTMMF_LAB
-            ++g_attn_fused_launches;
-#endif
-            const int nqp = ((a.Nq + 31) / 32) * 32, nkt = (a.Nk + 15) / 16, n_items = a.B * a.heads;
-            // all sixteen resident key tiles present (the 197- / 257-token towers): the persistent form, one workgroup per CU walking the items
-            const bool sm = a.sums != nullptr;
-            const bool persist = (nkt <= 16 || nqp == 288) && attn_fused_lds_bytes(a.Nq, a.Nk, false, sm) <= 160 * 1024;   // (a 17th key tile with other query counts: run-time chunk loops, spills in the persistent form)
-            const bool early = persist && nkt <= 8 && attn_fused_lds_bytes(a.Nq, a.Nk, true, sm) <= 160 * 1024;
-            const size_t lds = attn_fused_lds_bytes(a.Nq, a.Nk, early, sm);
-            if (a.items && !early) return ANTMMF_EINVAL;   // (the item table is read by the double-buffered persistent forms only -- ITQ0 ... ITNK --: attn_packed_ok)
-            unsigned pwgs = 256u;
-#ifdef ANTMMF_LAB
-            static const char* pw_env = ANTMMF_LAB_ENV("ANTMMF_ATTN_PERSIST_WGS");   // lab / emulator tests: a small grid makes every workgroup walk several items
-            if (pw_env) pwgs = (unsigned)atoi(pw_env);
-#endif
-            const dim3 pgrid(persist ? ((unsigned)n_items < pwgs ? (unsigned)n_items : pwgs) : (unsigned)n_items);
-#define BWDF_(NKS, HASE, FULL, NQC, PERS, ABL, EARLY, SUMS) do { set_lds(attn_bwd_fused64_kernel<NKS, HASE, FULL, NQC, PERS, ABL, EARLY, SUMS>, lds); \
-            hipLaunchKernelGGL((attn_bwd_fused64_kernel<NKS, HASE, FULL, NQC, PERS, ABL, EARLY, SUMS>), pgrid, block, lds, stream, a, nqp, n_items); } while (0)
-#define BWDF(NKS, HASE, FULL, NQC, PERS, ABL) do { if (sm && a.sums_v) BWDF_(NKS, HASE, FULL, NQC, PERS, 0, false, 1); else if (sm) BWDF_(NKS, HASE, FULL, NQC, PERS, 0, false, 2); \
-                                                   else BWDF_(NKS, HASE, FULL, NQC, PERS, ABL, false, 0); } while (0)
-#ifdef ANTMMF_LAB
-            static const char* abl_env = ANTMMF_LAB_ENV("ANTMMF_ATTN_FUSED_ABL");   // timing-only ablations of the 257-token kernel (wrong results)
-            const int abl = abl_env ? atoi(abl_env) : 0;
-            if (abl && !sm && persist && nkt > 16 && nqp == 288) {
-                switch (abl) {
-                    case 1: BWDF(8, true, true, 9, true, 1); return antmmf_check_launch();
-                    case 2: BWDF(8, true, true, 9, true, 2); return antmmf_check_launch();
-                    case 4: BWDF(8, true, true, 9, true, 4); return antmmf_check_launch();
-                    case 8: BWDF(8, true, true, 9, true, 8); return antmmf_check_launch();
-                    case 16: BWDF(8, true, true, 9, true, 16); return antmmf_check_launch();
-                    case 32: BWDF(8, true, true, 9, true, 32); return antmmf_check_launch();
-                    case 15: BWDF(8, true, true, 9, true, 15); return antmmf_check_launch();
-                    case 128: BWDF(8, true, true, 9, true, 128); return antmmf_check_launch();
-                    case 256: BWDF(8, true, true, 9, true, 256); return antmmf_check_launch();
-                    default: break;
-                }
+        if (p.form != ATTN_BWD_TWO_KERNEL) {
+#define BWDF3(NKS, HASE, FULL, NQC, PERS, EARLY) do { if (sums == 1) ATTN_BWDF(p, a, stream, NKS, HASE, FULL, NQC, PERS, 0, EARLY, 1); else if (sums) ATTN_BWDF(p, a, stream, NKS, HASE, FULL, NQC, PERS, 0, EARLY, 2); \
+                                                      else ATTN_BWDF(p, a, stream, NKS, HASE, FULL, NQC, PERS, 0, EARLY, 0); } while (0)
+            if (p.form == ATTN_BWD_FUSED_PER_ITEM) BWDF3(8, true, true, 0, false, false);
+            else if (p.hase) BWDF3(8, true, true, 9, true, false);
+            else if (p.full) BWDF3(8, false, true, 0, true, false);
+            else if (p.early) switch (p.nks) { case 4: BWDF3(4, false, false, 0, true, true); break; case 3: BWDF3(3, false, false, 0, true, true); break; default: BWDF3(2, false, false, 0, true, true); break; }
+            else switch (p.nks) {
+                case 8: BWDF3(8, false, false, 0, true, false); break; case 7: BWDF3(7, false, false, 0, true, false); break; case 6: BWDF3(6, false, false, 0, true, false); break;
+                case 5: BWDF3(5, false, false, 0, true, false); break; case 4: BWDF3(4, false, false, 0, true, false); break; case 3: BWDF3(3, false, false, 0, true, false); break;
+                default: BWDF3(2, false, false, 0, true, false); break;
             }
-#endif
-#ifdef ANTMMF_LAB
-            static const char* sa_env = ANTMMF_LAB_ENV("ANTMMF_ATTN_SUMS_ABL");   // timing-only (wrong sums): 16 no per-chunk dQ sums, 32 no end-of-item partials, 64 no finalisation
-            const int sa = sa_env ? atoi(sa_env) : 0;
-            if (sa && sm && persist && nkt > 16) {
-                switch (sa) {
-                    case 16: BWDF_(8, true, true, 9, true, 0, false, 2 | 16); return antmmf_check_launch();
-                    case 32: BWDF_(8, true, true, 9, true, 0, false, 2 | 32); return antmmf_check_launch();
-                    case 64: BWDF_(8, true, true, 9, true, 0, false, 2 | 64); return antmmf_check_launch();
-                    case 48: BWDF_(8, true, true, 9, true, 0, false, 2 | 48); return antmmf_check_launch();
-                    case 112: BWDF_(8, true, true, 9, true, 0, false, 2 | 112); return antmmf_check_launch();
-                    default: break;
-                }
-            }
-#endif
-            if (persist) {
-                if (nkt > 16) BWDF(8, true, true, 9, true, 0);
-                else if (nkt == 16) BWDF(8, false, true, 0, true, 0);
-                else if (nkt > 12) { if (nkt > 14) BWDF(8, false, false, 0, true, 0); else BWDF(7, false, false, 0, true, 0); }
-                else if (nkt > 8) { if (nkt > 10) BWDF(6, false, false, 0, true, 0); else BWDF(5, false, false, 0, true, 0); }
-                else if (early) {
-#define BWDE(NKS) do { if (sm && a.sums_v) BWDF_(NKS, false, false, 0, true, 0, true, 1); else if (sm) BWDF_(NKS, false, false, 0, true, 0, true, 2); else BWDF_(NKS, false, false, 0, true, 0, true, 0); } while (0)
-                    if (nkt > 6) BWDE(4); else if (nkt > 4) BWDE(3); else BWDE(2);
-#undef BWDE
-                }
-                else if (nkt > 6) BWDF(4, false, false, 0, true, 0);
-                else if (nkt > 4) BWDF(3, false, false, 0, true, 0);
-                else BWDF(2, false, false, 0, true, 0);
-            } else BWDF(8, true, true, 0, false, 0);
-#undef BWDF
-#undef BWDF_
+#undef BWDF3
             return antmmf_check_launch();
         }
     }
-    if (a.items) return ANTMMF_EINVAL;   // (no packed form of the two-kernel backward)
-#define BWDQ_K(KERN, LDS) do { set_lds(KERN, LDS); hipLaunchKernelGGL(KERN, grid, block, LDS, stream, a); } while (0)
-#define BWDQ(N) do { const size_t lds = (size_t)(32 * N) * (4 * DH) + (32 * N) * 4; \
-        if constexpr (DH == 64) { if (a.drop_thr) BWDQ_K((attn_bwd_dq64_kernel<N, true>), lds); else BWDQ_K((attn_bwd_dq64_kernel<N, false>), lds); } \
-        else { if (a.drop_thr) BWDQ_K((attn_bwd_dq_kernel<N, true, DH>), lds); else BWDQ_K((attn_bwd_dq_kernel<N, false, DH>), lds); } } while (0)
-    if (nch <= 1) BWDQ(1); else if (nch <= 3) BWDQ(3); else if (nch <= 7) BWDQ(7); else BWDQ(9);
+#define BWDQ(N) do { if constexpr (DH == 64) { if (a.drop_thr) ATTN_LAUNCH((attn_bwd_dq64_kernel<N, true>), p.grid, p.lds, stream, a); else ATTN_LAUNCH((attn_bwd_dq64_kernel<N, false>), p.grid, p.lds, stream, a); } \
+        else { if (a.drop_thr) ATTN_LAUNCH((attn_bwd_dq_kernel<N, true, DH>), p.grid, p.lds, stream, a); else ATTN_LAUNCH((attn_bwd_dq_kernel<N, false, DH>), p.grid, p.lds, stream, a); } } while (0)
+    switch (p.nch) { case 1: BWDQ(1); break; case 3: BWDQ(3); break; case 7: BWDQ(7); break; default: BWDQ(9); break; }
 #undef BWDQ
-#undef BWDQ_K
-    int rc = antmmf_check_launch();
+    const int rc = antmmf_check_launch();
     if (rc) return rc;
-    const int nqp = ((a.Nq + 31) / 32) * 32;
-    const size_t lds2 = (size_t)nqp * (4 * DH) + (size_t)nqp * 8;
-    if (a.drop_thr) { set_lds(attn_bwd_dkv_kernel<true, DH>, lds2); hipLaunchKernelGGL((attn_bwd_dkv_kernel<true, DH>), grid, block, lds2, stream, a, nqp); }
-    else { set_lds(attn_bwd_dkv_kernel<false, DH>, lds2); hipLaunchKernelGGL((attn_bwd_dkv_kernel<false, DH>), grid, block, lds2, stream, a, nqp); }
+    const size_t lds2 = (size_t)p.nqp * (4 * DH) + (size_t)p.nqp * 8;
+    if (a.drop_thr) ATTN_LAUNCH((attn_bwd_dkv_kernel<true, DH>), p.grid, lds2, stream, a, p.nqp); else ATTN_LAUNCH((attn_bwd_dkv_kernel<false, DH>), p.grid, lds2, stream, a, p.nqp);
     return antmmf_check_launch();
 }
+
+// The one filler of AttnArgs and the one holder of the pointer, stride and alignment rules: every entry point passes what it has (nullptr / 0 for the rest)
+struct AttnLd { long q, k, v, o, d_o, dq, dk, dv; };
+static AttnArgs attn_args(const void* q, const void* k, const void* v, const float* key_bias, const int* items, const void* o, const float* lse, const void* d_o,
+                          void* dq, void* dk, void* dv, float* sums, int want_dv, int B, int heads, int Nq, int Nk, const AttnLd& ld, float scale,
+                          float dropout_p, uint64_t dropout_seed) {
+    AttnArgs a{};
+    a.drop_thr = dropout_threshold(dropout_p); a.drop_scale = 1.0f / (1.0f - dropout_p); a.drop_seed = dropout_seed;
+    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.key_bias = key_bias; a.items = items; a.o = (bf16_t*)const_cast<void*>(o);
+    a.lse = const_cast<float*>(lse); a.d_o = (const bf16_t*)d_o; a.dq = (bf16_t*)dq; a.dk = (bf16_t*)dk; a.dv = (bf16_t*)dv;
+    a.ldq = ld.q; a.ldk = ld.k; a.ldv = ld.v; a.ldo = ld.o; a.lddo = ld.d_o; a.lddq = ld.dq; a.lddk = ld.dk; a.lddv = ld.dv;
+    a.B = B; a.heads = heads; a.Nq = Nq; a.Nk = Nk; a.scale = scale; a.sums = sums; a.sums_v = want_dv ? 1 : 0;
+    return a;
+}
+static bool attn_operands_ok(const AttnArgs& a, bool bwd) {
+    if (!a.q || !a.k || !a.v || !a.o || !a.lse || (a.ldq & 7) || (a.ldk & 7) || (a.ldv & 7) || (a.ldo & 3)) return false;
+    if (!bwd) return true;
+    if (!a.d_o || !a.dq || !a.dk || !a.dv || (a.lddo & 7) || (a.lddq & 3) || (a.lddk & 3) || (a.lddv & 3) || (a.ldo & 7)) return false;
+    // 16-byte operand vectors (and LDS-DMA pieces), 8-byte gradient stores
+    return !((((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v | (uintptr_t)a.d_o | (uintptr_t)a.o) & 15) || (((uintptr_t)a.dq | (uintptr_t)a.dk | (uintptr_t)a.dv) & 7));
+}
+static int attn_fwd(const AttnArgs& a, int head_dim, hipStream_t stream) { return head_dim == 64 ? attn_fwd_launch<64>(a, stream) : head_dim == 128 ? attn_fwd_launch<128>(a, stream) : ANTMMF_EINVAL; }
+static int attn_bwd(const AttnArgs& a, int head_dim, hipStream_t stream) { return head_dim == 64 ? attn_bwd_launch<64>(a, stream) : head_dim == 128 ? attn_bwd_launch<128>(a, stream) : ANTMMF_EINVAL; }
 
 extern "C" int antmmf_attention_fwd_hd(const void* q, const void* k, const void* v, const float* key_bias, void* o, float* lse,
                                        int B, int heads, int head_dim, int Nq, int Nk, long ldq, long ldk, long ldv, long ldo, float scale,
                                        float dropout_p, uint64_t dropout_seed, hipStream_t stream) {
-    AttnArgs a{};
     if (!(dropout_p >= 0.f && dropout_p < 1.f)) return ANTMMF_EINVAL;
-    a.drop_thr = dropout_threshold(dropout_p); a.drop_scale = 1.0f / (1.0f - dropout_p); a.drop_seed = dropout_seed;
-    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.key_bias = key_bias; a.o = (bf16_t*)o; a.lse = lse;
-    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.B = B; a.heads = heads; a.Nq = Nq; a.Nk = Nk; a.scale = scale;
-    if (!q || !k || !v || !o || !lse || !attn_args_ok(a, head_dim)) return ANTMMF_EINVAL;
-    a.fwd_stagger = 0;
-#ifdef ANTMMF_LAB
-    static const char* st_env = ANTMMF_LAB_ENV("ANTMMF_ATTN_FWD_STAGGER");
-    if (st_env) a.fwd_stagger = atoi(st_env);
-#endif
-    return head_dim == 64 ? attn_fwd_launch<64>(a, stream) : attn_fwd_launch<128>(a, stream);
+    const AttnArgs a = attn_args(q, k, v, key_bias, nullptr, o, lse, nullptr, nullptr, nullptr, nullptr, nullptr, 0, B, heads, Nq, Nk, {ldq, ldk, ldv, ldo}, scale, dropout_p, dropout_seed);
+    return attn_operands_ok(a, false) ? attn_fwd(a, head_dim, stream) : ANTMMF_EINVAL;
 }
 
 extern "C" int antmmf_attention_bwd_hd(const void* q, const void* k, const void* v, const float* key_bias, const void* o, const float* lse,
                                        const void* d_o, void* dq, void* dk, void* dv, int B, int heads, int head_dim, int Nq, int Nk, long ldq, long ldk,
                                        long ldv, long ldo, long lddo, long lddq, long lddk, long lddv, float scale, float dropout_p,
                                        uint64_t dropout_seed, hipStream_t stream) {
-    AttnArgs a{};
     if (!(dropout_p >= 0.f && dropout_p < 1.f)) return ANTMMF_EINVAL;
-    a.drop_thr = dropout_threshold(dropout_p); a.drop_scale = 1.0f / (1.0f - dropout_p); a.drop_seed = dropout_seed;
-    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.key_bias = key_bias; a.o = (bf16_t*)const_cast<void*>(o);
-    a.lse = const_cast<float*>(lse); a.d_o = (const bf16_t*)d_o; a.dq = (bf16_t*)dq; a.dk = (bf16_t*)dk; a.dv = (bf16_t*)dv;
-    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.lddo = lddo; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
-    a.B = B; a.heads = heads; a.Nq = Nq; a.Nk = Nk; a.scale = scale;
-    if (!q || !k || !v || !o || !lse || !d_o || !dq || !dk || !dv || !attn_args_ok(a, head_dim) || (lddo & 7) || (lddq & 3) || (lddk & 3) || (lddv & 3) || (ldo & 7))
-        return ANTMMF_EINVAL;
-    if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)d_o | (uintptr_t)o) & 15) || (((uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) & 7))
-        return ANTMMF_EINVAL;   // 16-byte operand vectors (and LDS-DMA pieces), 8-byte gradient stores
-    return head_dim == 64 ? attn_bwd_launch<64>(a, stream) : attn_bwd_launch<128>(a, stream);
+    const AttnArgs a = attn_args(q, k, v, key_bias, nullptr, o, lse, d_o, dq, dk, dv, nullptr, 0, B, heads, Nq, Nk, {ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv}, scale, dropout_p, dropout_seed);
+    return attn_operands_ok(a, true) ? attn_bwd(a, head_dim, stream) : ANTMMF_EINVAL;
 }
 
 // head size 64: the entry points every tower of the contrastive path uses
@@ -1659,26 +1671,13 @@ extern "C" int antmmf_attention_bwd(const void* q, const void* k, const void* v,
 // over dQ | dK | dV (one tensor pass each per layer) disappear.  Served by the one-kernel backward only (head size 64, 33 ... 272 keys, no dropout):
 // antmmf_attention_bwd_sums_ok says whether a shape is; anything else is ANTMMF_EINVAL (the caller then sums the columns of dq / dk / dv itself).
 extern "C" int antmmf_attention_bwd_sums_ok(int head_dim, int Nq, int Nk, float dropout_p) {
-    AttnArgs a{};
-    float dummy = 0.f;
-    a.Nq = Nq; a.Nk = Nk; a.drop_thr = (dropout_p > 0.f) ? 1u : 0u; a.sums = &dummy;
-    return head_dim == 64 && Nq > 0 && Nq <= 288 && Nk > 0 && attn_fused_ok(a) ? 1 : 0;
+    return attn_bwd_plan(head_dim, 1, 1, Nq, Nk, dropout_p > 0.f, false, 1, 256u).form != ATTN_BWD_NONE ? 1 : 0;
 }
 extern "C" int antmmf_attention_bwd_sums(const void* q, const void* k, const void* v, const float* key_bias, const void* o, const float* lse,
                                          const void* d_o, void* dq, void* dk, void* dv, float* sums, int want_dv, int B, int heads, int Nq, int Nk, long ldq, long ldk,
                                          long ldv, long ldo, long lddo, long lddq, long lddk, long lddv, float scale, hipStream_t stream) {
-    AttnArgs a{};
-    a.drop_thr = 0; a.drop_scale = 1.0f; a.drop_seed = 0;
-    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.key_bias = key_bias; a.o = (bf16_t*)const_cast<void*>(o);
-    a.lse = const_cast<float*>(lse); a.d_o = (const bf16_t*)d_o; a.dq = (bf16_t*)dq; a.dk = (bf16_t*)dk; a.dv = (bf16_t*)dv;
-    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.lddo = lddo; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
-    a.B = B; a.heads = heads; a.Nq = Nq; a.Nk = Nk; a.scale = scale; a.sums = sums; a.sums_v = want_dv ? 1 : 0;
-    if (!q || !k || !v || !o || !lse || !d_o || !dq || !dk || !dv || !sums || !attn_args_ok(a, 64) || (lddo & 7) || (lddq & 3) || (lddk & 3) || (lddv & 3) || (ldo & 7))
-        return ANTMMF_EINVAL;
-    if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)d_o | (uintptr_t)o) & 15) || (((uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) & 7))
-        return ANTMMF_EINVAL;
-    if (!attn_fused_ok(a)) return ANTMMF_EINVAL;
-    return attn_bwd_launch<64>(a, stream);
+    const AttnArgs a = attn_args(q, k, v, key_bias, nullptr, o, lse, d_o, dq, dk, dv, sums, want_dv, B, heads, Nq, Nk, {ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv}, scale, 0.f, 0);
+    return sums && attn_operands_ok(a, true) ? attn_bwd(a, 64, stream) : ANTMMF_EINVAL;
 }
 
 // ---- token-packed self-attention ------------------------------------------------------------------------------------------------------------------
@@ -1688,37 +1687,19 @@ extern "C" int antmmf_attention_bwd_sums(const void* q, const void* k, const voi
 // written.  Same kernels as the strided entry points (AttnArgs::items): an item computes exactly what the strided form computes for it under a key_bias that is -inf
 // from its length on.  Served: head size 64, 33 ... 128 tokens (the forward's resident tiles and the double-buffered persistent one-kernel backward), no dropout.
 static bool attn_packed_ok(int head_dim, int n_max) {
-    if (head_dim != 64 || n_max <= 32 || n_max > 128) return false;
-    AttnArgs a{};
-    float dummy = 0.f;
-    a.Nq = a.Nk = n_max; a.sums = &dummy;
-    return attn_fused_ok(a) && attn_fused_lds_bytes(n_max, n_max, true, true) <= 160 * 1024;
+    return attn_fwd_plan(head_dim, 1, 1, n_max, n_max, true) && attn_bwd_plan(head_dim, 1, 1, n_max, n_max, false, true, 1, 256u).form != ATTN_BWD_NONE;
 }
 extern "C" int antmmf_attention_packed_ok(int head_dim, int n_max) { return attn_packed_ok(head_dim, n_max) ? 1 : 0; }
 extern "C" int antmmf_attention_fwd_packed(const void* q, const void* k, const void* v, const int* items, void* o, float* lse, int B, int heads, int n_max,
                                            long ldq, long ldk, long ldv, long ldo, float scale, hipStream_t stream) {
-    AttnArgs a{};
-    a.drop_thr = 0; a.drop_scale = 1.0f;
-    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (bf16_t*)o; a.lse = lse; a.items = items;
-    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.B = B; a.heads = heads; a.Nq = n_max; a.Nk = n_max; a.scale = scale;
-    if (!q || !k || !v || !o || !lse || !items || !attn_args_ok(a, 64) || !attn_packed_ok(64, n_max)) return ANTMMF_EINVAL;
-    return attn_fwd_launch<64>(a, stream);
+    const AttnArgs a = attn_args(q, k, v, nullptr, items, o, lse, nullptr, nullptr, nullptr, nullptr, nullptr, 0, B, heads, n_max, n_max, {ldq, ldk, ldv, ldo}, scale, 0.f, 0);
+    return items && attn_operands_ok(a, false) && attn_packed_ok(64, n_max) ? attn_fwd(a, 64, stream) : ANTMMF_EINVAL;
 }
 static int attn_bwd_packed(const void* q, const void* k, const void* v, const int* items, const void* o, const float* lse, const void* d_o, void* dq, void* dk,
                            void* dv, float* sums, int want_dv, int B, int heads, int n_max, long ldq, long ldk, long ldv, long ldo, long lddo, long lddq,
                            long lddk, long lddv, float scale, hipStream_t stream) {
-    AttnArgs a{};
-    a.drop_thr = 0; a.drop_scale = 1.0f;
-    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (bf16_t*)const_cast<void*>(o); a.items = items;
-    a.lse = const_cast<float*>(lse); a.d_o = (const bf16_t*)d_o; a.dq = (bf16_t*)dq; a.dk = (bf16_t*)dk; a.dv = (bf16_t*)dv;
-    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.lddo = lddo; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
-    a.B = B; a.heads = heads; a.Nq = n_max; a.Nk = n_max; a.scale = scale; a.sums = sums; a.sums_v = want_dv ? 1 : 0;
-    if (!q || !k || !v || !o || !lse || !d_o || !dq || !dk || !dv || !items || !attn_args_ok(a, 64) || (lddo & 7) || (lddq & 3) || (lddk & 3) || (lddv & 3) || (ldo & 7))
-        return ANTMMF_EINVAL;
-    if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)d_o | (uintptr_t)o) & 15) || (((uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) & 7))
-        return ANTMMF_EINVAL;
-    if (!attn_packed_ok(64, n_max)) return ANTMMF_EINVAL;
-    return attn_bwd_launch<64>(a, stream);
+    const AttnArgs a = attn_args(q, k, v, nullptr, items, o, lse, d_o, dq, dk, dv, sums, want_dv, B, heads, n_max, n_max, {ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv}, scale, 0.f, 0);
+    return items && attn_operands_ok(a, true) && attn_packed_ok(64, n_max) ? attn_bwd(a, 64, stream) : ANTMMF_EINVAL;
 }
 extern "C" int antmmf_attention_bwd_packed(const void* q, const void* k, const void* v, const int* items, const void* o, const float* lse, const void* d_o, void* dq,
                                            void* dk, void* dv, int B, int heads, int n_max, long ldq, long ldk, long ldv, long ldo, long lddo, long lddq, long lddk,
@@ -1732,6 +1713,8 @@ extern "C" int antmmf_attention_bwd_sums_packed(const void* q, const void* k, co
     if (!sums) return ANTMMF_EINVAL;
     return attn_bwd_packed(q, k, v, items, o, lse, d_o, dq, dk, dv, sums, want_dv, B, heads, n_max, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv, scale, stream);
 }
+#undef ATTN_BWDF
+#undef ATTN_LAUNCH
 
 // ---- key importance: column sums of the attention probabilities --------------------------------------------------------------------------------
 // out[b][k] += weight * sum_h sum_q P_drop[b][h][q][k]  -- what the reference does with the attention MAPS it asks the text tower for in training

@@ -528,6 +528,60 @@ def case_attention(ops, dev, B=2, heads=2, Nq=17, Nk=17, bias_kind="none", packe
         assert torch.equal(sums2[:, :2 * D], sums[:, :2 * D]) and bool((sums2[:, 2 * D:] == 7.0).all()), tag + ": sums without dV"
 
 
+# The "is it served" queries against what the entry points do, at the sizes where the answer changes: 32 | 33 keys (two-kernel | one-kernel backward), 128 | 129
+# (the longest packed item), 272 | 273 (the one-kernel backward's largest row).  A refusal is ANTMMF_EINVAL from the host side, before any launch.
+ATTN_SERVED_CASES = [("strided", n) for n in (32, 33, 128, 129, 272, 273)] + [("packed", n) for n in (32, 33, 128, 129)]
+
+
+def _served(call):
+    """True: the library ran `call`; False: it refused it with ANTMMF_EINVAL.  Anything else propagates."""
+    try:
+        call()
+    except RuntimeError as e:
+        if "code -22" not in str(e):
+            raise
+        return False
+    return True
+
+
+def case_attention_served(ops, dev, kind, n, B=2, heads=2, seed=70):
+    """attention_bwd_sums_ok == "attention_bwd(..., sums=...) returns" and attention_packed_ok == "attention_fwd_packed / attention_bwd_packed return" (two items of
+    n and 1 tokens), for no sums, q | k | v sums and q | k sums; where the backward runs with and without the sums, dq / dk / dv are the same bits."""
+    D = heads * 64
+    scale = 0.125
+    packed = kind == "packed"
+    lead = (n + 1,) if packed else (B, n)
+    qkv = q(rnd(lead + (3 * D,), seed)).to(dev, BF)
+    qd, kd, vd = qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:]
+    d_o = q(rnd(lead + (D,), seed + 1)).to(dev, BF)
+    tag = f"attn.served[{kind},{n}]"
+    if packed:
+        items = torch.tensor([[0, n], [n, 1]], dtype=torch.int32, device=dev)
+        ok = ops.attention_packed_ok(64, n)
+        fwd = []
+        assert _served(lambda: fwd.extend(ops.attention_fwd_packed(qd, kd, vd, items, heads, scale, n))) == ok, tag + ": attention_packed_ok vs attention_fwd_packed"
+        o, lse = fwd if ok else (torch.zeros(n + 1, D, dtype=BF, device=dev), torch.zeros(B, heads, n, device=dev))
+        ok_sums = ok
+
+        def bwd(sums, sums_v=True):
+            g = torch.zeros_like(qkv)
+            return ops.attention_bwd_packed(qd, kd, vd, items, o, lse, d_o, heads, scale, n, g[:, :D], g[:, D:2 * D], g[:, 2 * D:], sums=sums, sums_v=sums_v)
+    else:
+        ok, ok_sums = True, ops.attention_bwd_sums_ok(64, n, n)   # (every size up to 288 has a plain backward)
+        o, lse = ops.attention_fwd(qd, kd, vd, heads, scale)
+
+        def bwd(sums, sums_v=True):
+            return ops.attention_bwd(qd, kd, vd, o, lse, d_o, heads, scale, sums=sums, sums_v=sums_v)
+    plain = []
+    assert _served(lambda: plain.extend(bwd(None))) == ok, tag + ": the backward without sums"
+    for sums_v in (True, False):
+        got = []
+        sums = torch.zeros(B, 3 * D, dtype=torch.float32, device=dev)
+        assert _served(lambda: got.extend(bwd(sums, sums_v))) == ok_sums, tag + f": the query vs the backward with sums (dV third: {sums_v})"
+        if ok and ok_sums:
+            assert all(torch.equal(a, b) for a, b in zip(got, plain)), tag + ": gradients differ with sums requested"
+
+
 # ------------------------------------------------------------------------------ losses
 def case_milnce(ops, dev, Bg=6, n=2, world=2):
     """Row-sharded MIL-NCE over `world` simulated ranks == oracle loss on the tiled global matrix, and the

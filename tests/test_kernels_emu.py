@@ -321,6 +321,12 @@ def test_attention_backward_rejects_misaligned_operands(ops):
         ops.attention_bwd(q_bad, k, v, o, lse, d_o, h, 0.125)
 
 
+@pytest.mark.parametrize("kind,n", kc.ATTN_SERVED_CASES)
+def test_attention_served_queries_match_entry_points(ops, kind, n):
+    """ops.attention_bwd_sums_ok / ops.attention_packed_ok say exactly what the entry points then do (one head fewer than the hardware twin: emulator time)."""
+    kc.case_attention_served(ops, DEV, kind, n, heads=1)
+
+
 def test_attention_cross_multichunk(ops):
     kc.case_attention(ops, DEV, B=1, heads=1, Nq=21, Nk=77, bias_kind="bert", packed=False)
 

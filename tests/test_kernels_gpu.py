@@ -284,6 +284,12 @@ def test_attention(ops, cfg):
     kc.case_attention(ops, DEV, **cfg)
 
 
+@pytest.mark.parametrize("kind,n", kc.ATTN_SERVED_CASES)
+def test_attention_served_queries_match_entry_points(ops, kind, n):
+    """ops.attention_bwd_sums_ok / ops.attention_packed_ok say exactly what the entry points then do."""
+    kc.case_attention_served(ops, DEV, kind, n)
+
+
 def test_attention_backward_one_kernel_runs_and_repeats():
     """attn_bwd_fused64_kernel at the ViT-L/14 tower's shape (16 heads x 257 tokens, packed qkv rows; 640 (b, h) items on the 256 persistent workgroups: two or three items
     each, the next one's operands prefetched into the rows the current one has finished with): the lab library's counter says that kernel served the call, two calls
