@@ -280,24 +280,30 @@ def l2_normalize(x, eps=1e-12):
 
 class _Attention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, key_bias, heads, scale, dropout_p, seed):
+    def forward(ctx, q, k, v, key_bias, heads, scale, dropout_p, seed, want_probs=False):
         o, lse = ops.attention_fwd(q, k, v, heads, scale, key_bias, dropout_p=dropout_p, dropout_seed=seed)
         ctx.save_for_backward(q, k, v, o, lse, key_bias)
         ctx.meta = (heads, scale, dropout_p, seed)
-        return o
+        if not want_probs:
+            return o
+        probs = ops.attention_probs(q, k, lse, heads, scale, key_bias, dropout_p=dropout_p, dropout_seed=seed)   # this forward's lse and seed: its own map
+        ctx.mark_non_differentiable(probs)
+        return o, probs
 
     @staticmethod
-    def backward(ctx, d_o):
+    def backward(ctx, d_o, *_):
         q, k, v, o, lse, key_bias = ctx.saved_tensors
         heads, scale, dropout_p, seed = ctx.meta
         dq, dk, dv = ops.attention_bwd(q, k, v, o, lse, d_o.contiguous(), heads, scale, key_bias, dropout_p=dropout_p, dropout_seed=seed)
-        return dq, dk, dv, None, None, None, None, None
+        return dq, dk, dv, None, None, None, None, None, None
 
 
-def attention(q, k, v, heads, scale, key_bias=None, dropout_p=0.0, seed=0):
+def attention(q, k, v, heads, scale, key_bias=None, dropout_p=0.0, seed=0, return_probs=False):
     """softmax(scale q k^T + key_bias) v on [B, N, heads*dh] bf16 tensors, head size dh = 64 or 128 (views of a packed projection are fine).  dropout_p > 0:
-    attention-probability dropout inside the kernel, its counter-based mask of `seed` regenerated in backward."""
-    return _Attention.apply(q, k, v, key_bias, heads, scale, dropout_p, seed)
+    attention-probability dropout inside the kernel, its counter-based mask of `seed` regenerated in backward.
+    return_probs: -> (ctx, probs), probs the fp32 [B, heads, Nq, Nk] (post-dropout) probabilities of this very forward -- rebuilt by one extra launch from its
+    lse and seed (ops.attention_probs); detached, no graph output."""
+    return _Attention.apply(q, k, v, key_bias, heads, scale, dropout_p, seed, return_probs)
 
 
 # ------------------------------------------------------------------------------ fused transformer layer
@@ -417,6 +423,9 @@ if os.environ.get("ANTMMF_FFN_FOLD"):   # rounds 3 - 4 read this variable; since
 # Collector for the one thing the reference does with attention MAPS on this path (univl_video_base.py:131-143: words_importance = sum over layers of the
 # head-mean attention, summed over the queries): a [B, N] fp32 tensor while a BertEncoder runs with output_attentions=True, None otherwise.
 KEY_IMPORTANCE = None
+# Collector for the maps themselves (BertEncoder with output_attentions="maps", modeling_bert.py:283-314 of the reference: one [B, heads, N, N] tensor per layer,
+# after dropout): a list while such an encoder runs -- every layer appends its fp32 map, rebuilt from its forward's lse and seed by ops.attention_probs -- None otherwise.
+ATTENTION_MAPS = None
 
 
 def set_ffn_fold(flag):
@@ -478,8 +487,8 @@ class _TransformerLayer(torch.autograd.Function):
         seed = int(seed or 0)
         if text is not None:
             # token-packed input [T, d] (PackedText): every row kernel and GEMM below sees T rows instead of B * n_max; only the attention calls know about items
-            if x.dim() != 2 or x.shape[0] != text.rows or key_bias is not None or p_att > 0 or KEY_IMPORTANCE is not None:
-                raise ValueError("transformer_layer: a packed input is [rows, d] with its PackedText table, no key_bias, no attention dropout, no key-importance collector")
+            if x.dim() != 2 or x.shape[0] != text.rows or key_bias is not None or p_att > 0 or KEY_IMPORTANCE is not None or ATTENTION_MAPS is not None:
+                raise ValueError("transformer_layer: a packed input is [rows, d] with its PackedText table, no key_bias, no attention dropout, no key-importance or attention-map collector")
             B, N, d = 1, x.shape[0], x.shape[1]
         else:
             B, N, d = x.shape
@@ -503,6 +512,9 @@ class _TransformerLayer(torch.autograd.Function):
         if KEY_IMPORTANCE is not None:   # `output_attentions=True` callers: the head-mean column sums of this layer's probabilities join the collector
             q3 = qkv.view(B, N, 3 * d)
             ops.attention_key_importance_(KEY_IMPORTANCE, q3[..., :d], q3[..., d:2 * d], lse, spec.heads, scale, key_bias, p_att, seed or 0, weight=1.0 / spec.heads)
+        if ATTENTION_MAPS is not None:   # `output_attentions="maps"` callers: this layer's [B, heads, N, N] probabilities, only on request (one extra launch)
+            q3 = qkv.view(B, N, 3 * d)
+            ATTENTION_MAPS.append(ops.attention_probs(q3[..., :d], q3[..., d:2 * d], lse, spec.heads, scale, key_bias, p_att, seed or 0))
         o2 = o.view(T, d)
         st_in = None
         if spec.kind == "m2":

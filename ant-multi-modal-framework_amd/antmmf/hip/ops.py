@@ -587,10 +587,50 @@ def attention_key_importance_(out, q, k, lse, heads, scale, key_bias=None, dropo
     _dev_ok(out, q, k, lse, key_bias); _f32(out, "out"); _c(out, "out"); _c(lse, "lse")
     B, Nq, D = q.shape
     Nk = k.shape[1]
-    assert _head_dim(D, heads) == 64 and tuple(out.shape) == (B, Nk)
+    assert tuple(out.shape) == (B, Nk)
+    if _head_dim(D, heads) != 64:   # head size 128: the importance output of the probability-map kernel (head size 64 keeps its own kernel family)
+        attention_probs_into(q, k, lse, heads, scale, key_bias, dropout_p, dropout_seed, importance=out, weight=weight)
+        return out
     _rc(_lib.load().antmmf_attention_key_importance(_p(q), _p(k), _p(key_bias), _p(lse), _p(out), B, heads, Nq, Nk, _tok_ld(q, "q"), _tok_ld(k, "k"), float(scale),
                                                     float(dropout_p), int(dropout_seed), float(weight), _stream()), "antmmf_attention_key_importance")
     return out
+
+
+ATTN_MAX_TOKENS = 288   # the attention kernels' whole-row limit (queries and keys)
+
+
+def attention_probs_into(q, k, lse, heads, scale, key_bias=None, dropout_p=0.0, dropout_seed=0, probs=None, importance=None, weight=1.0):
+    """The (post-dropout) attention probabilities of (q, k), rebuilt from the forward's `lse` and seed -- see antmmf_attention_probs: written to `probs`
+    [B, heads, Nq, Nk] fp32 and / or accumulated, summed over heads and queries and times `weight`, into `importance` [B, Nk] fp32.  At least one output."""
+    _dev_ok(q, k, lse, key_bias, probs, importance)
+    B, Nq, D = q.shape
+    Nk = k.shape[1]
+    dh = _head_dim(D, heads)
+    if probs is None and importance is None:
+        raise ValueError("attention_probs: neither the maps nor the importance output was given")
+    if not (1 <= Nq <= ATTN_MAX_TOKENS and 1 <= Nk <= ATTN_MAX_TOKENS):
+        raise ValueError(f"attention_probs: {Nq} queries x {Nk} keys is beyond the attention kernels' whole-row limit of {ATTN_MAX_TOKENS} tokens")
+    _f32(lse, "lse"); _c(lse, "lse")
+    assert tuple(lse.shape) == (B, heads, Nq) and tuple(k.shape) == (B, Nk, D)
+    if key_bias is not None:
+        _f32(key_bias, "key_bias"); _c(key_bias, "key_bias")
+        assert tuple(key_bias.shape) == (B, Nk)
+    if probs is not None:
+        _f32(probs, "probs"); _c(probs, "probs")
+        assert tuple(probs.shape) == (B, heads, Nq, Nk)
+    if importance is not None:
+        _f32(importance, "importance"); _c(importance, "importance")
+        assert tuple(importance.shape) == (B, Nk)
+    _rc(_lib.load().antmmf_attention_probs(_p(q), _p(k), _p(key_bias), _p(lse), _p(probs), _p(importance), B, heads, dh, Nq, Nk, _tok_ld(q, "q"), _tok_ld(k, "k"),
+                                           float(scale), float(dropout_p), int(dropout_seed), float(weight), _stream()), "antmmf_attention_probs")
+
+
+def attention_probs(q, k, lse, heads, scale, key_bias=None, dropout_p=0.0, dropout_seed=0):
+    """-> fp32 [B, heads, Nq, Nk]: softmax(scale q k^T + key_bias) with the forward's dropout applied (dropped elements 0, kept ones / (1 - p)), from the `lse`
+    that attention_fwd returned for the same q, k, key_bias, dropout_p and dropout_seed.  Head size 64 or 128, at most 288 queries and keys."""
+    probs = torch.empty(q.shape[0], heads, q.shape[1], k.shape[1], dtype=torch.float32, device=q.device)
+    attention_probs_into(q, k, lse, heads, scale, key_bias, dropout_p, dropout_seed, probs=probs)
+    return probs
 
 
 def attention_bwd_sums_ok(head_dim, Nq, Nk, dropout_p=0.0):

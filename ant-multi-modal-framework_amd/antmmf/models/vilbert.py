@@ -8,10 +8,13 @@ forward signature / return triple as the reference.
 
 MI355X design: per stream ONE packed [3 A, d_in] projection GEMM (the reference issues three), then the fused attention kernel twice with
 the streams swapped -- stream-2 queries over stream-1 keys / values under stream 1's additive mask, and vice versa -- with the
-attention-probability dropout of each direction applied INSIDE the kernel from a counter-based mask (nothing [B, h, Nq, Nk]-shaped reaches HBM).
+attention-probability dropout of each direction applied INSIDE the kernel from a counter-based mask (something [B, h, Nq, Nk]-shaped reaches HBM only on request:
+`visualization=True`).
 The additive masks are the reference's extended masks `[B, 1, 1, N]` (0 / -10000); they are passed to the kernel as per-key biases [B, N].
 Head size: 64 (every tower of the contrastive path) or 128 (ViLBERT's own bi_hidden_size 1024 / 8 heads); another
-`bi_hidden_size / bi_num_attention_heads` raises NotImplementedError.  `visualization=True` (returning the probability tensors) is not available from the fused kernel and raises."""
+`bi_hidden_size / bi_num_attention_heads` raises NotImplementedError.  `visualization=True` returns the reference's `attn_data` dict (vilbert.py:402-414): both
+directions' (post-dropout) probabilities, fp32, rebuilt from each forward's lse and seed by one extra launch per direction (antmmf_attention_probs), and
+[B, heads, N, dh] views of the packed query / key projections.  With visualization off nothing extra runs."""
 import math
 
 import torch
@@ -62,8 +65,6 @@ class BertBiAttention(nn.Module):
 
     def forward(self, input_tensor1, attention_mask1, input_tensor2, attention_mask2, co_attention_mask=None, use_co_attention_mask=False,
                 dropout_seeds=None):
-        if self.visualization:
-            raise NotImplementedError("visualization=True needs the probability tensors, which the fused kernel never materialises")
         q1, k1, v1 = self._qkv(input_tensor1, self.query1, self.key1, self.value1)   # vision stream
         q2, k2, v2 = self._qkv(input_tensor2, self.query2, self.key2, self.value2)   # text stream
         scale = 1.0 / math.sqrt(self.attention_head_size)
@@ -76,6 +77,16 @@ class BertBiAttention(nn.Module):
         s1, s2 = dropout_seeds if dropout_seeds is not None else (0, 0)
         h = self.num_attention_heads
         # context 1: text queries over vision keys / values (reference :357-376); context 2: vision queries over text (:378-401)
-        ctx1 = HF.attention(q2, k1, v1, h, scale, b1, p1, s1)
-        ctx2 = HF.attention(q1, k2, v2, h, scale, b2, p2, s2)
-        return ctx1, ctx2, None
+        if not self.visualization:
+            ctx1 = HF.attention(q2, k1, v1, h, scale, b1, p1, s1)
+            ctx2 = HF.attention(q1, k2, v2, h, scale, b2, p2, s2)
+            return ctx1, ctx2, None
+        ctx1, attn1 = HF.attention(q2, k1, v1, h, scale, b1, p1, s1, return_probs=True)
+        ctx2, attn2 = HF.attention(q1, k2, v2, h, scale, b2, p2, s2, return_probs=True)
+
+        def heads_of(t):   # transpose_for_scores (reference :318-325) as a view of the packed projection: [B, N, h dh] -> [B, h, N, dh]
+            return t.detach().view(t.shape[0], t.shape[1], h, self.attention_head_size).permute(0, 2, 1, 3)
+
+        # the reference's keys, its spelling of the fifth included (:405-412)
+        attn_data = {"attn1": attn1, "queries1": heads_of(q2), "keys1": heads_of(k1), "attn2": attn2, "querues2": heads_of(q1), "keys2": heads_of(k2)}
+        return ctx1, ctx2, attn_data

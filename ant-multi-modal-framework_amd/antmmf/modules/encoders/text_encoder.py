@@ -8,8 +8,9 @@ HF BertModel names (embeddings.word_embeddings ... encoder.layer.N.attention.sel
 `pytorch_model.bin` / `model.safetensors` of a BERT checkpoint loads key for key (a leading `bert.` is dropped; heads the model does not
 have -- `cls.*` -- are ignored).  Same constructor arguments, same attributes (`embeddings`, `encoder`, `pooler`, `module`, `config`),
 same forward triple.  Differences, stated: nothing is downloaded (a missing checkpoint directory is an error); `output_attentions=True`
-returns, in the place of the attention maps (which never reach HBM on the fused path), their reduction `KeyImportance` -- the sum over layers of
-the head-mean attention summed over the queries, which is all the caller derives from them (`words_importance`, univl_video_base.py:138-143);
+returns, in the place of the attention maps (which reach HBM only on request), their reduction `KeyImportance` -- the sum over layers of
+the head-mean attention summed over the queries, which is all the caller derives from them (`words_importance`, univl_video_base.py:138-143) -- and
+`output_attentions="maps"` the reference's tuple of per-layer [B, heads, N, N] maps itself (BertEncoder.forward);
 `model_type` other than "bert" is out of scope."""
 import json
 import os
@@ -67,7 +68,7 @@ class _FusedBert(BertModel):
         x = self.embeddings(input_ids=input_ids, inputs_embeds=inputs_embeds, token_type_ids=token_type_ids, position_ids=position_ids)
         enc = self.encoder(x, key_bias, head_mask=None, output_attentions=output_attentions)
         seq = enc[0]
-        if output_attentions:   # third output: modeling_bert.KeyImportance in the place of the attention maps (see BertEncoder.forward)
+        if output_attentions:   # third output: modeling_bert.KeyImportance in the place of the attention maps, or ("maps") the maps themselves (see BertEncoder.forward)
             return seq, self.pooler(seq), enc[-1]
         return seq, self.pooler(seq)
 

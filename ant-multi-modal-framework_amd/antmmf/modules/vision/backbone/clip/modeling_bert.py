@@ -114,14 +114,25 @@ class BertEncoder(nn.Module):
         self.layer = nn.ModuleList([BertLayer(config) for _ in range(config.num_hidden_layers)])
 
     def forward(self, hidden_states, attention_mask=None, head_mask=None, output_attentions=None):
-        """output_attentions (constructor flag or call argument): the attention MAPS of the reference ([B, heads, N, N] per layer, modeling_bert.py:283-314)
-        never reach HBM on the fused path.  What comes back in their place is the reduction their only consumer on this path applies
-        (UnivlVideoBase.forward_text_encoder, univl_video_base.py:138-143): `KeyImportance` = sum over layers of the head-mean attention summed over the
-        queries, a [B, N] fp32 tensor gathered by the attention kernels' sibling antmmf_attention_key_importance (post-dropout probabilities, as HF returns)."""
-        want_att = self.output_attentions if output_attentions is None else bool(output_attentions)
+        """output_attentions (constructor flag -- through BertConfig -- or call argument):
+        * True: the attention MAPS of the reference ([B, heads, N, N] per layer, modeling_bert.py:283-314) are not written.  What comes back in their place is the
+          reduction their only consumer on the training path applies (UnivlVideoBase.forward_text_encoder, univl_video_base.py:138-143): `KeyImportance` = sum over
+          layers of the head-mean attention summed over the queries, a [B, N] fp32 tensor gathered by the attention kernels' sibling
+          antmmf_attention_key_importance (post-dropout probabilities, as HF returns).
+        * "maps": the reference's tuple itself, one fp32 [B, heads, N, N] tensor per layer (after dropout, detached), rebuilt on request from each layer's q, k,
+          lse and seed by antmmf_attention_probs (one extra launch per layer; a fully masked query row is zeros, not NaN).  Hidden states are those of a run
+          without the flag."""
+        want_att = self.output_attentions if output_attentions is None else output_attentions
+        want_maps = isinstance(want_att, str)
+        if want_maps and want_att != "maps":
+            raise ValueError(f"output_attentions: {want_att!r} (False, True for KeyImportance, or \"maps\" for the per-layer attention maps)")
+        want_att = bool(want_att)
         all_hidden = ()
-        importance = None
-        if want_att:
+        importance = maps = None
+        if want_maps:
+            maps = []
+            HF.ATTENTION_MAPS = maps
+        elif want_att:
             importance = torch.zeros(hidden_states.shape[:2], dtype=torch.float32, device=hidden_states.device)
             HF.KEY_IMPORTANCE = importance
         try:
@@ -131,10 +142,13 @@ class BertEncoder(nn.Module):
                 hidden_states = layer(hidden_states, attention_mask, None)
         finally:
             HF.KEY_IMPORTANCE = None
+            HF.ATTENTION_MAPS = None
         outputs = (hidden_states,)
         if self.output_hidden_states:
             outputs = outputs + (all_hidden + (hidden_states,),)
-        if want_att:
+        if want_maps:
+            outputs = outputs + (tuple(maps),)
+        elif want_att:
             outputs = outputs + (KeyImportance(importance),)
         return outputs
 

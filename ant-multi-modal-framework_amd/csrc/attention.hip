@@ -4,7 +4,7 @@
 // everywhere (SURVEY.md 2.4 K3, section 5 "long-context: absent"), so this is a whole-row design, not
 // a streaming flash kernel: one workgroup owns one (batch, head), parks that head's K and V (<= 288
 // keys, 37 KiB each) in LDS once, and each wave walks 16-query tiles with the full score row held in
-// registers.  No [B*h, N, N] tensor ever reaches HBM (the reference materialises it three times:
+// registers.  A [B*h, N, N] tensor reaches HBM only on request (attn_probs_kernel at the end of this file; the reference materialises it three times:
 // modeling_bert.py:144-161, multihead_attention.py:120-145, nn.MultiheadAttention's math path).
 //
 // MFMA bookkeeping (v_mfma_f32_16x16x32_bf16; A: lane l holds A[l&15][8g+e], B: lane l holds B[8g+e][l&15],
@@ -1624,8 +1624,10 @@ static AttnArgs attn_args(const void* q, const void* k, const void* v, const flo
     a.B = B; a.heads = heads; a.Nq = Nq; a.Nk = Nk; a.scale = scale; a.sums = sums; a.sums_v = want_dv ? 1 : 0;
     return a;
 }
+// what every kernel that rebuilds the scores needs: q, k, the forward's lse, 16-byte rows
+static bool attn_qk_ok(const AttnArgs& a) { return a.q && a.k && a.lse && !(a.ldq & 7) && !(a.ldk & 7); }
 static bool attn_operands_ok(const AttnArgs& a, bool bwd) {
-    if (!a.q || !a.k || !a.v || !a.o || !a.lse || (a.ldq & 7) || (a.ldk & 7) || (a.ldv & 7) || (a.ldo & 3)) return false;
+    if (!attn_qk_ok(a) || !a.v || !a.o || (a.ldv & 7) || (a.ldo & 3)) return false;
     if (!bwd) return true;
     if (!a.d_o || !a.dq || !a.dk || !a.dv || (a.lddo & 7) || (a.lddq & 3) || (a.lddk & 3) || (a.lddv & 3) || (a.ldo & 7)) return false;
     // 16-byte operand vectors (and LDS-DMA pieces), 8-byte gradient stores
@@ -1719,7 +1721,7 @@ extern "C" int antmmf_attention_bwd_sums_packed(const void* q, const void* k, co
 // ---- key importance: column sums of the attention probabilities --------------------------------------------------------------------------------
 // out[b][k] += weight * sum_h sum_q P_drop[b][h][q][k]  -- what the reference does with the attention MAPS it asks the text tower for in training
 // (`output_attentions=True`, prj/base_vtp/roi_univl/univl/model/univl_video_base.py:131-143: cat over layers of the head mean, summed over layers and
-// queries -> words_importance).  The maps never exist here; the probabilities are rebuilt from Q, K and the forward's log-sum-exp exactly as the backward
+// queries -> words_importance).  The maps are not written for this (only on request: attn_probs_kernel below); the probabilities are rebuilt from Q, K and the forward's log-sum-exp exactly as the backward
 // kernels do (same dropout mask: HF's BertSelfAttention returns the probabilities AFTER dropout), summed over the queries in registers, over the 16 query
 // lanes by DPP, over the waves in LDS, and leave as one atomic add per (b, h, key).  Head size 64.
 template <int NCH, bool DROP>
@@ -1796,3 +1798,118 @@ extern "C" int antmmf_attention_key_importance(const void* q, const void* k, con
     return antmmf_check_launch();
 }
 
+// ---- attention probability maps, on request -----------------------------------------------------------------------------------------------------
+// probs[b][h][q][k] = P_drop (fp32, dense [B, heads, Nq, Nk]) and / or importance[b][k] += weight * sum_h sum_q P_drop -- the tensors the reference hands back
+// from BertSelfAttention / BertEncoder with `output_attentions=True` (modeling_bert.py:144-161, 283-314: one map per layer, AFTER dropout, as HuggingFace does),
+// from BertBiAttention(visualization=True) (vilbert.py:360-414: `attn1` / `attn2`), and their reduction words_importance (univl_video_base.py:131-143).  The
+// forward and backward kernels never write them; this sibling rebuilds P = exp2(scale log2e q.k + key_bias log2e - lse log2e) from Q, K and the forward's
+// log-sum-exp exactly as attn_key_importance_kernel above does (K staged once into the swizzled LDS tile, scores transposed, 16-query tiles per wave, the same
+// DROPOUT_KEEP counter -- so the mask is the forward's), and runs only when a caller asks for the maps.
+// ONE instantiation serves everything: head size (64 / 128), dropout, the number of 16-key tiles and the choice of outputs are run-time, wave-uniform values.  The
+// key tiles are a run-time loop whose four probabilities per lane are used and dropped (no per-thread array is indexed by a run-time value: no scratch): stored
+// per lane -- a lane holds 4 consecutive keys of one query, 16 B where the element index is a multiple of 4 and all four keys exist (Nk is often odd: 77, 257),
+// scalar stores otherwise -- and, for the importance, reduced over the 16 query lanes and added into the LDS column strip.
+// Deviation from the reference, the rule of attn_key_importance_kernel: a fully masked query row (lse = -inf) is a row of ZEROS (the reference's softmax gives NaN
+// under -inf masks and a uniform row under -10000 ones); query rows at or beyond Nq do not exist.  Every element of a valid row is written, zeros included.
+template <int DH>
+__device__ __forceinline__ void attn_probs_body(const AttnArgs& a, float* __restrict__ probs, float* __restrict__ importance, float weight, int nkt, char* smem) {
+    constexpr int RB = 2 * DH, NS = DH / 8, KM = DH / 32;
+    const int nkp = 16 * nkt;
+    char* Ks = smem;
+    float* kb = reinterpret_cast<float*>(Ks + nkp * RB);
+    float* colsum = kb + nkp;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, grp = lane >> 4;
+    const int b = blockIdx.x / a.heads, h = blockIdx.x % a.heads;
+    // K -> swizzled token tile (rows >= Nk zero): up to nine 16-B vectors per thread, four requested before the first is written (stage_rows' rule, its trip count
+    // a run-time value here)
+    const bf16_t* ksrc = a.k + (long)b * a.Nk * a.ldk + h * DH;
+    const int nvec = nkp * NS;
+    for (int base = threadIdx.x; base < nvec; base += 4 * ATTN_THREADS) {
+        uint4 v[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int id = base + i * ATTN_THREADS, row = id / NS, slot = id % NS;
+            v[i] = (id < nvec && row < a.Nk) ? *reinterpret_cast<const uint4*>(ksrc + (long)row * a.ldk + slot * 8) : make_uint4(0, 0, 0, 0);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int id = base + i * ATTN_THREADS, row = id / NS, slot = id % NS;
+            if (id < nvec) *reinterpret_cast<uint4*>(Ks + row * RB + ((slot ^ attn_swz<DH>(row)) << 4)) = v[i];
+        }
+    }
+    stage_key_bias(kb, a, b, nkp);
+    if (importance) for (int i = threadIdx.x; i < nkp; i += ATTN_THREADS) colsum[i] = 0.f;
+    __syncthreads();
+    const float scale2 = a.scale * LOG2E;
+    const int nqt = (a.Nq + 15) >> 4;
+    const bool al16 = !((uintptr_t)probs & 15);
+    for (int qt = wave; qt < nqt; qt += ATTN_THREADS / 64) {
+        const int qi = qt * 16 + l15;
+        const int qrow = qi < a.Nq ? qi : a.Nq - 1;
+        const bf16_t* qp = a.q + ((long)b * a.Nq + qrow) * a.ldq + h * DH + grp * 8;
+        bf16x8_t qf[KM];
+#pragma unroll
+        for (int j = 0; j < KM; ++j) qf[j] = load_frag_global(qp + 32 * j);
+        const float lse = a.lse[((long)b * a.heads + h) * a.Nq + qrow];
+        // padding queries and fully masked ones (lse = -inf) contribute and store zeros: subtracting +inf makes every exponent -inf
+        const float lse2 = (qi >= a.Nq || lse == -INFINITY) ? INFINITY : lse * LOG2E;
+        const long e0 = (((long)b * a.heads + h) * a.Nq + qrow) * a.Nk;   // first element of this query's row: of probs, and of the forward's dropout counter
+        const uint32_t dbase = (uint32_t)e0;
+        for (int t = 0; t < nkt; ++t) {
+            const int key = 16 * t + 4 * grp;
+            f32x4_t sa = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int j = 0; j < KM; ++j) sa = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows<DH>(Ks, 16 * t + l15, 4 * j + grp), qf[j], sa, 0, 0, 0);
+            const float4 bias = *reinterpret_cast<const float4*>(kb + key);
+            const float bb[4] = {bias.x, bias.y, bias.z, bias.w};
+            float pr[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) pr[r] = EXP2F(sa[r] * scale2 + bb[r] - lse2);
+            if (a.drop_thr) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) pr[r] = DROPOUT_KEEP(dbase + key + r, a.drop_seed, a.drop_thr) ? pr[r] * a.drop_scale : 0.f;
+            }
+            if (probs && qi < a.Nq) {
+                float* p = probs + e0 + key;
+                if (al16 && !((e0 + key) & 3) && key + 3 < a.Nk) *reinterpret_cast<float4*>(p) = make_float4(pr[0], pr[1], pr[2], pr[3]);
+                else {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (key + r < a.Nk) p[r] = pr[r];
+                }
+            }
+            if (importance) {   // (wave-uniform: every lane takes part in the DPP sums)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float v = row16_sum(pr[r]);   // over the wave's 16 query lanes
+                    if (l15 == 0) atomicAdd(colsum + key + r, v);
+                }
+            }
+        }
+    }
+    if (importance) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < a.Nk; i += ATTN_THREADS) atomicAdd(importance + (long)b * a.Nk + i, colsum[i] * weight);
+    }
+}
+
+__global__ __launch_bounds__(ATTN_THREADS, 2) void attn_probs_kernel(const AttnArgs a, float* __restrict__ probs, float* __restrict__ importance, float weight,
+                                                                     int head_dim, int nkt) {
+    ANTMMF_DYN_LDS(char, smem);
+    if (head_dim == 64) attn_probs_body<64>(a, probs, importance, weight, nkt, smem);
+    else attn_probs_body<128>(a, probs, importance, weight, nkt, smem);
+}
+
+extern "C" int antmmf_attention_probs(const void* q, const void* k, const float* key_bias, const float* lse, float* probs, float* importance, int B, int heads,
+                                      int head_dim, int Nq, int Nk, long ldq, long ldk, float scale, float dropout_p, uint64_t dropout_seed, float weight,
+                                      hipStream_t stream) {
+    if (!(dropout_p >= 0.f && dropout_p < 1.f) || (!probs && !importance)) return ANTMMF_EINVAL;
+    const AttnArgs a = attn_args(q, k, nullptr, key_bias, nullptr, nullptr, lse, nullptr, nullptr, nullptr, nullptr, nullptr, 0, B, heads, Nq, Nk, {ldq, ldk}, scale,
+                                 dropout_p, dropout_seed);
+    if (!attn_shape_ok(head_dim, B, heads, Nq, Nk) || !attn_qk_ok(a) || (((uintptr_t)q | (uintptr_t)k) & 15)) return ANTMMF_EINVAL;
+    const int nkt = (Nk + 15) / 16;
+    const size_t lds = (size_t)(16 * nkt) * (2 * head_dim + 8);   // K tile, key bias, column sums: 74.25 KiB at 288 keys of head size 128 (two workgroups per CU)
+    set_lds(attn_probs_kernel, lds);
+    hipLaunchKernelGGL(attn_probs_kernel, dim3((unsigned)(B * heads)), dim3(ATTN_THREADS), lds, stream, a, probs, importance, weight, head_dim, nkt);
+    return antmmf_check_launch();
+}

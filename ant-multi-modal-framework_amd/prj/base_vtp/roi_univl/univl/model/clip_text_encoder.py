@@ -14,13 +14,17 @@ from antmmf.modules.vision.backbone.clip.modeling_bert import BertModel
 
 
 class BertModel2(BertModel):
-    def forward(self, input_ids, attention_mask=None, token_type_ids=None, position_ids=None, head_mask=None):
+    def forward(self, input_ids, attention_mask=None, token_type_ids=None, position_ids=None, head_mask=None, output_attentions=False):
+        """output_attentions (True / "maps", see BertEncoder.forward) adds the encoder's last output as a third one."""
         if attention_mask is None:
             attention_mask = torch.ones_like(input_ids)
         # additive key bias: 0 where attended, -10000 where masked (reference :86-100), kept per key: [B, N] fp32
         key_bias = (1.0 - attention_mask.float()) * -10000.0
         x = self.embeddings(input_ids, token_type_ids=token_type_ids, position_ids=position_ids)
-        seq = self.encoder(x, key_bias, head_mask=None)[0]
+        enc = self.encoder(x, key_bias, head_mask=None, output_attentions=output_attentions)
+        seq = enc[0]
+        if output_attentions:
+            return seq, seq[:, 0, :], enc[-1]
         return seq, seq[:, 0, :]
 
 
@@ -70,7 +74,7 @@ class RobertBertEncoder(nn.Module):
             self.text_projection.data.copy_(proj)
 
     def forward(self, input_ids, attention_mask, token_type_ids=None, position_ids=None, head_mask=None, output_attentions=False):
-        seq, cls = self.module(input_ids, attention_mask, token_type_ids, position_ids, head_mask)
+        seq, cls, *att = self.module(input_ids, attention_mask, token_type_ids, position_ids, head_mask, output_attentions=output_attentions)
         if self.text_projection is not None:
-            return seq, HF.linear(cls.contiguous(), self.text_projection, weight_layout="io")
-        return seq, cls
+            cls = HF.linear(cls.contiguous(), self.text_projection, weight_layout="io")
+        return (seq, cls, *att)   # att: KeyImportance (output_attentions=True) or the tuple of per-layer maps ("maps"); absent otherwise

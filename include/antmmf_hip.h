@@ -225,8 +225,18 @@ int antmmf_attention_bwd(const void* q, const void* k, const void* v, const floa
 int antmmf_attention_key_importance(const void* q, const void* k, const float* key_bias, const float* lse, float* out, int B, int heads,
                                     int Nq, int Nk, int64_t ldq, int64_t ldk, float scale, float dropout_p, uint64_t dropout_seed,
                                     float weight, antmmf_stream_t stream);
-/* The same pair with an explicit head size: 64 or 128 (ViLBERT's bi_hidden_size 1024 / 8 heads, antmmf/models/vilbert.py:326-339); element
- * (b, n, h, e) lives at base + (b*N + n)*ld + h*head_dim + e.  The two entry points above are head_dim = 64. */
+/* Attention probability MAPS on request, head size 64 or 128, Nq, Nk <= 288: the (post-dropout) probabilities rebuilt from q, k and the forward's lse (same
+ * dropout_p / dropout_seed as the forward: the same mask) -- what the reference returns from BertSelfAttention / BertEncoder with output_attentions=True
+ * (modeling_bert.py:144-161, 283-314), as `attn1` / `attn2` of BertBiAttention(visualization=True) (vilbert.py:360-414), and reduces to words_importance
+ * (univl_video_base.py:131-143).  Two outputs, each optional, at least one given (ANTMMF_EINVAL otherwise): probs [B, heads, Nq, Nk] fp32, dense, every
+ * element written (dropped ones 0, kept ones scaled by 1 / (1 - p)); importance [B, Nk] fp32 += weight * sum over heads and queries (atomics: the semantics of
+ * antmmf_attention_key_importance).  A fully masked query row (lse = -inf) is a row of zeros (the reference: NaN / a uniform row).  q, k 16-byte aligned, ldq /
+ * ldk multiples of 8.  Off the training step's path: one launch, only when asked for. */
+int antmmf_attention_probs(const void* q, const void* k, const float* key_bias, const float* lse, float* probs, float* importance, int B, int heads,
+                           int head_dim, int Nq, int Nk, int64_t ldq, int64_t ldk, float scale, float dropout_p, uint64_t dropout_seed, float weight,
+                           antmmf_stream_t stream);
+/* The forward / backward pair with an explicit head size: 64 or 128 (ViLBERT's bi_hidden_size 1024 / 8 heads, antmmf/models/vilbert.py:326-339); element
+ * (b, n, h, e) lives at base + (b*N + n)*ld + h*head_dim + e.  antmmf_attention_fwd / antmmf_attention_bwd are head_dim = 64. */
 int antmmf_attention_fwd_hd(const void* q, const void* k, const void* v, const float* key_bias, void* o, float* lse,
                             int B, int heads, int head_dim, int Nq, int Nk, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo,
                             float scale, float dropout_p, uint64_t dropout_seed, antmmf_stream_t stream);
