@@ -57,6 +57,7 @@ _SIGNATURES = {
     "antmmf_gemm_bf16_gated_colsum": [P, P, P, I, I, I, L, L, L, P, L, P, P],
     "antmmf_attention_bwd_sums_ok": [I, I, I, F],
     "antmmf_attention_packed_ok": [I, I],
+    "antmmf_attention_limits": [P, P],
     "antmmf_attention_fwd_packed": [P, P, P, P, P, P, I, I, I, L, L, L, L, F, P],
     "antmmf_attention_bwd_packed": [P, P, P, P, P, P, P, P, P, P, I, I, I, L, L, L, L, L, L, L, L, F, P],
     "antmmf_attention_bwd_sums_packed": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, L, L, L, L, L, L, L, L, F, P],

@@ -302,7 +302,9 @@ def attention(q, k, v, heads, scale, key_bias=None, dropout_p=0.0, seed=0, retur
     """softmax(scale q k^T + key_bias) v on [B, N, heads*dh] bf16 tensors, head size dh = 64 or 128 (views of a packed projection are fine).  dropout_p > 0:
     attention-probability dropout inside the kernel, its counter-based mask of `seed` regenerated in backward.
     return_probs: -> (ctx, probs), probs the fp32 [B, heads, Nq, Nk] (post-dropout) probabilities of this very forward -- rebuilt by one extra launch from its
-    lse and seed (ops.attention_probs); detached, no graph output."""
+    lse and seed (ops.attention_probs); detached, no graph output.
+    Rows of up to 4096 queries and keys are served (beyond 288 on either side by the streamed kernels, ops.attention_limits); return_probs keeps the whole-row
+    limit of 288 (ops.ATTN_MAX_TOKENS) and raises ValueError on a longer row."""
     return _Attention.apply(q, k, v, key_bias, heads, scale, dropout_p, seed, return_probs)
 
 
@@ -425,6 +427,7 @@ if os.environ.get("ANTMMF_FFN_FOLD"):   # rounds 3 - 4 read this variable; since
 KEY_IMPORTANCE = None
 # Collector for the maps themselves (BertEncoder with output_attentions="maps", modeling_bert.py:283-314 of the reference: one [B, heads, N, N] tensor per layer,
 # after dropout): a list while such an encoder runs -- every layer appends its fp32 map, rebuilt from its forward's lse and seed by ops.attention_probs -- None otherwise.
+# Both collectors keep the whole-row limit of 288 tokens (ops.ATTN_MAX_TOKENS): on a longer row, which the layers themselves serve, they raise.
 ATTENTION_MAPS = None
 
 

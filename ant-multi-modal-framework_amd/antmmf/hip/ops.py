@@ -563,13 +563,34 @@ def _head_dim(D, heads):
     return D // heads
 
 
+def attention_limits():
+    """(whole-row limit, streamed limit) of the attention kernels in tokens per row, queries and keys alike, read from the loaded library: rows up to the first run
+    in the whole-row kernels -- the only form of the packed entry points, the token sums, the probability maps and the key importance --, rows up to the second in
+    the streamed forward and backward."""
+    lib = _lib.load()
+    lim = getattr(lib, "antmmf_attention_limits_read", None)   # kept on the handle: one query per loaded library
+    if lim is None:
+        v = [ctypes.c_int(0) for _ in range(2)]
+        _rc(lib.antmmf_attention_limits(*(ctypes.byref(x) for x in v)), "antmmf_attention_limits")
+        lim = lib.antmmf_attention_limits_read = tuple(x.value for x in v)
+    return lim
+
+
+def _attn_rows_ok(name, Nq, Nk):
+    limit = attention_limits()[1]
+    if Nq > limit or Nk > limit:
+        raise ValueError(f"{name}: {Nq} queries x {Nk} keys, the attention kernels serve at most {limit} tokens per row (antmmf_attention_limits: streamed)")
+
+
 def attention_fwd(q, k, v, heads, scale, key_bias=None, dropout_p=0.0, dropout_seed=0):
     """dropout_p > 0: attention-probability dropout with the counter-based mask of (dropout_seed, element index).  Head size =
-    q.shape[-1] / heads: 64 or 128."""
+    q.shape[-1] / heads: 64 or 128.  Rows of up to attention_limits()[0] = 288 queries and keys run in the whole-row kernels, longer ones (one side or both, up to
+    attention_limits()[1] = 4096) in the streamed ones; beyond that: ValueError."""
     _dev_ok(q, k, v, key_bias)
     B, Nq, D = q.shape
     Nk = k.shape[1]
     dh = _head_dim(D, heads)
+    _attn_rows_ok("attention_fwd", Nq, Nk)
     o = torch.empty(B, Nq, D, dtype=torch.bfloat16, device=q.device)
     lse = torch.empty(B, heads, Nq, dtype=torch.float32, device=q.device)
     if key_bias is not None:
@@ -588,7 +609,7 @@ def attention_key_importance_(out, q, k, lse, heads, scale, key_bias=None, dropo
     B, Nq, D = q.shape
     Nk = k.shape[1]
     assert tuple(out.shape) == (B, Nk)
-    if _head_dim(D, heads) != 64:   # head size 128: the importance output of the probability-map kernel (head size 64 keeps its own kernel family)
+    if _head_dim(D, heads) != 64:   # head size 128: the importance output of the probability-map kernel (head size 64: its own entry point, the same kernel)
         attention_probs_into(q, k, lse, heads, scale, key_bias, dropout_p, dropout_seed, importance=out, weight=weight)
         return out
     _rc(_lib.load().antmmf_attention_key_importance(_p(q), _p(k), _p(key_bias), _p(lse), _p(out), B, heads, Nq, Nk, _tok_ld(q, "q"), _tok_ld(k, "k"), float(scale),
@@ -596,7 +617,7 @@ def attention_key_importance_(out, q, k, lse, heads, scale, key_bias=None, dropo
     return out
 
 
-ATTN_MAX_TOKENS = 288   # the attention kernels' whole-row limit (queries and keys)
+ATTN_MAX_TOKENS = 288   # the attention kernels' whole-row limit (queries and keys): the limit of the probability maps and the key importance (attention_limits()[0])
 
 
 def attention_probs_into(q, k, lse, heads, scale, key_bias=None, dropout_p=0.0, dropout_seed=0, probs=None, importance=None, weight=1.0):
@@ -627,14 +648,16 @@ def attention_probs_into(q, k, lse, heads, scale, key_bias=None, dropout_p=0.0, 
 
 def attention_probs(q, k, lse, heads, scale, key_bias=None, dropout_p=0.0, dropout_seed=0):
     """-> fp32 [B, heads, Nq, Nk]: softmax(scale q k^T + key_bias) with the forward's dropout applied (dropped elements 0, kept ones / (1 - p)), from the `lse`
-    that attention_fwd returned for the same q, k, key_bias, dropout_p and dropout_seed.  Head size 64 or 128, at most 288 queries and keys."""
+    that attention_fwd returned for the same q, k, key_bias, dropout_p and dropout_seed.  Head size 64 or 128, at most 288 queries and keys (ATTN_MAX_TOKENS: the
+    maps exist for whole rows only, also where the streamed forward serves a longer row -- ValueError)."""
     probs = torch.empty(q.shape[0], heads, q.shape[1], k.shape[1], dtype=torch.float32, device=q.device)
     attention_probs_into(q, k, lse, heads, scale, key_bias, dropout_p, dropout_seed, probs=probs)
     return probs
 
 
 def attention_bwd_sums_ok(head_dim, Nq, Nk, dropout_p=0.0):
-    """True when attention_bwd(..., sums=...) is served: the one-kernel backward's shapes (today head size 64, no dropout, 33 ... 272 keys; the library decides)."""
+    """True when attention_bwd(..., sums=...) is served: the one-kernel backward's shapes (today head size 64, no dropout, 33 ... 272 keys; the library decides).
+    Never for a row beyond the whole-row limit: the streamed backward has no token sums."""
     return bool(_lib.load().antmmf_attention_bwd_sums_ok(int(head_dim), int(Nq), int(Nk), float(dropout_p)))
 
 
@@ -653,6 +676,7 @@ def _attention_bwd(name, q, k, v, o, lse, d_o, heads, scale, dq, dk, dv, key_bia
             raise ValueError(f"{name}: lse must be [B, heads, n_max]")
     else:
         B, Nq, Nk, ld = q.shape[0], q.shape[1], k.shape[1], _tok_ld
+        _attn_rows_ok(name, Nq, Nk)
     if (packed or sums is not None) and (dh != 64 or dropout_p):   # (their entry points take neither argument; every other limit is the library's to report)
         raise ValueError(f"{name}: the packed form and the token sums exist for head size 64 without dropout only")
     sum_args = ()
@@ -697,7 +721,7 @@ def _items_ok(items, name="items"):
 
 
 def attention_packed_ok(head_dim, n_max):
-    """True when the packed entry points serve items of up to n_max tokens (today head size 64, 33 ... 128; the library decides)."""
+    """True when the packed entry points serve items of up to n_max tokens (today head size 64, 33 ... 128; the library decides; never beyond the whole-row limit)."""
     return bool(_lib.load().antmmf_attention_packed_ok(int(head_dim), int(n_max)))
 
 

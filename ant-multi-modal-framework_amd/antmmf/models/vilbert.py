@@ -14,7 +14,9 @@ The additive masks are the reference's extended masks `[B, 1, 1, N]` (0 / -10000
 Head size: 64 (every tower of the contrastive path) or 128 (ViLBERT's own bi_hidden_size 1024 / 8 heads); another
 `bi_hidden_size / bi_num_attention_heads` raises NotImplementedError.  `visualization=True` returns the reference's `attn_data` dict (vilbert.py:402-414): both
 directions' (post-dropout) probabilities, fp32, rebuilt from each forward's lse and seed by one extra launch per direction (antmmf_attention_probs), and
-[B, heads, N, dh] views of the packed query / key projections.  With visualization off nothing extra runs."""
+[B, heads, N, dh] views of the packed query / key projections.  With visualization off nothing extra runs.
+Streams of more than 288 tokens or regions (up to 4096) are served by the streamed attention kernels; `visualization=True` on such a stream raises ValueError: the
+maps exist for rows of at most 288 tokens (ops.ATTN_MAX_TOKENS)."""
 import math
 
 import torch

@@ -121,7 +121,9 @@ class BertEncoder(nn.Module):
           antmmf_attention_key_importance (post-dropout probabilities, as HF returns).
         * "maps": the reference's tuple itself, one fp32 [B, heads, N, N] tensor per layer (after dropout, detached), rebuilt on request from each layer's q, k,
           lse and seed by antmmf_attention_probs (one extra launch per layer; a fully masked query row is zeros, not NaN).  Hidden states are those of a run
-          without the flag."""
+          without the flag.
+        Rows of more than 288 tokens (up to 4096) run through the streamed attention kernels; with True or "maps" such a row raises (ValueError for the maps, the library's refusal for the importance) -- the maps and
+        the key importance exist for rows of at most 288 tokens (ops.ATTN_MAX_TOKENS)."""
         want_att = self.output_attentions if output_attentions is None else output_attentions
         want_maps = isinstance(want_att, str)
         if want_maps and want_att != "maps":

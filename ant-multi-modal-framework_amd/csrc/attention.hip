@@ -1,10 +1,15 @@
-// attention.hip -- fused multi-head attention (forward + backward) for short sequences on gfx950.
+// attention.hip -- fused multi-head attention (forward + backward) on gfx950: whole-row kernels up to 288 tokens, streamed kernels up to 4096.
 //
-// The contrastive towers never see more than 257 image tokens / 77 text tokens and head_dim is 64
-// everywhere (SURVEY.md 2.4 K3, section 5 "long-context: absent"), so this is a whole-row design, not
+// The contrastive towers of the bench configs never see more than 257 image tokens / 77 text tokens at head size 64
+// (SURVEY.md 2.4 K3, section 5 "long-context: absent"), so the kernels the training step runs are a whole-row design, not
 // a streaming flash kernel: one workgroup owns one (batch, head), parks that head's K and V (<= 288
 // keys, 37 KiB each) in LDS once, and each wave walks 16-query tiles with the full score row held in
-// registers.  A [B*h, N, N] tensor reaches HBM only on request (attn_probs_kernel at the end of this file; the reference materialises it three times:
+// registers.  Rows beyond 288 tokens on either side (ViT-L/14 at 336 / 448 px: 577 / 1025 tokens, M2 at a larger image_size, long merged
+// cross-encoder rows, ViLBERT with many regions) run in three streamed siblings -- attn_fwd_stream_kernel (online softmax), attn_bwd_dq_stream_kernel,
+// attn_bwd_dkv_stream_kernel: "streamed forms" below -- built from the same tiles, swizzle and fragment bookkeeping: a workgroup per (batch, head, 128-token
+// block), the other side walked through LDS in blocks.  attn_fwd_plan / attn_bwd_plan choose; a shape within 288 x 288 keeps exactly its whole-row kernel.
+// The packed entry points, the token sums, the probability maps and the key importance exist in whole-row form only (288).
+// A [B*h, N, N] tensor reaches HBM only on request (attn_probs_kernel at the end of this file; the reference materialises it three times:
 // modeling_bert.py:144-161, multihead_attention.py:120-145, nn.MultiheadAttention's math path).
 //
 // MFMA bookkeeping (v_mfma_f32_16x16x32_bf16; A: lane l holds A[l&15][8g+e], B: lane l holds B[8g+e][l&15],
@@ -125,19 +130,19 @@ __device__ __forceinline__ void stage_rows(char* dst, const bf16_t* __restrict__
 // two tiles at once (K and V, or Q and dO): all loads of both in flight together
 template <int DH, int NPAD>
 __device__ __forceinline__ void stage_rows2(char* dst0, const bf16_t* __restrict__ src0, long ld0, char* dst1, const bf16_t* __restrict__ src1, long ld1,
-                                            int n_valid, int n_pad) {
+                                            int n_valid, int n_pad, int tid = threadIdx.x) {
     constexpr int NS = DH / 8, TRIPS = (NPAD * NS + ATTN_THREADS - 1) / ATTN_THREADS;
     uint4 v0[TRIPS], v1[TRIPS];
 #pragma unroll
     for (int i = 0; i < TRIPS; ++i) {
-        const int id = threadIdx.x + i * ATTN_THREADS, row = id / NS, slot = id % NS;
+        const int id = tid + i * ATTN_THREADS, row = id / NS, slot = id % NS;
         const bool ok = id < n_pad * NS && row < n_valid;
         v0[i] = ok ? *reinterpret_cast<const uint4*>(src0 + (long)row * ld0 + slot * 8) : make_uint4(0, 0, 0, 0);
         v1[i] = ok ? *reinterpret_cast<const uint4*>(src1 + (long)row * ld1 + slot * 8) : make_uint4(0, 0, 0, 0);
     }
 #pragma unroll
     for (int i = 0; i < TRIPS; ++i) {
-        const int id = threadIdx.x + i * ATTN_THREADS, row = id / NS, slot = id % NS;
+        const int id = tid + i * ATTN_THREADS, row = id / NS, slot = id % NS;
         if (id < n_pad * NS) {
             const int off = row * (2 * DH) + ((slot ^ attn_swz<DH>(row)) << 4);
             *reinterpret_cast<uint4*>(dst0 + off) = v0[i];
@@ -877,6 +882,333 @@ __global__ __launch_bounds__(ATTN_THREADS, DH == 64 ? 2 : 1) void attn_bwd_dkv_k
     }
 }
 
+// ---- streamed forms: rows longer than 288 tokens (ViT-L/14 at 336 px: 577, at 448 px: 1025; long merged cross-encoder rows) --------------------------------
+// The whole-row kernels above park ALL keys (or all queries) of a head in LDS, which ends at 288 tokens.  These three walk the other side in LDS-resident blocks
+// instead: one workgroup per (b, h, block of ATTN_STREAM_QB = 128 tokens), each of its 8 waves owns ONE 16-token tile of that block for the whole kernel -- its
+// operands and accumulators stay in registers -- and a run-time loop stages block after block of the opposite side (ATTN_STREAM_KEYS(DH) tokens: 256 at head size
+// 64, 128 at head size 128 -- 64 KiB of token tiles + two fp32 rows: 67584 B = 66 KiB at head size 64, two workgroups per CU; 66560 B = 65 KiB at head size 128) through the same swizzled tiles, fragment reads and
+// MFMA bookkeeping.  Head size is the only template parameter: dropout, the key bias, the block count and the tail are run-time, wave-uniform values (a key / query
+// tile past the end of the last block is skipped by a wave-uniform branch; rows between the end and the next multiple of 32 are staged as zeros and masked).
+//   forward:  online softmax over the key blocks (running maximum m and sum in the exp2 domain, O rescaled by exp2(m_old - m_new) per block).  A block that is
+//             masked entirely before any valid key was seen leaves m = -inf: the rescale factor is then 1 and the exponent's subtrahend 0 (exp2(-inf - -inf) would be
+//             NaN).  A fully masked query row ends as in attn_fwd_kernel: o = 0, lse = -inf.
+//   dQ:       attn_bwd_dq_kernel with an outer loop over key blocks: P from the saved lse, D = <dO, O> once per query, dQ accumulated in registers, stored once.
+//   dK / dV:  one workgroup per (b, h, block of 128 KEYS), attn_bwd_dkv_kernel's body with an outer loop over query blocks (Q, dO, -lse, -D staged per block).
+// No atomics: every output element is produced by one lane in a fixed order (bit-reproducible).  The dropout counter is the whole-row kernels' expression.
+#define ATTN_STREAM_QB 128
+#define ATTN_STREAM_KEYS(DH) (16384 / (DH))
+#define ATTN_STREAM_MAX_TOKENS 4096
+// The staging addresses and the fragment offsets of a block are loop invariants: hipcc computes all of them (the global ones 64-bit, two per 16-B vector) in front of
+// the block loop and keeps them alive through both phases -- at head size 64 that is what pushed the kernels past 128 VGPRs into scratch.  With a row stride and a thread
+// index the compiler cannot see through, re-read per block, they are formed where they are used and die there (a few VALU instructions per block).
+#ifdef ANTMMF_EMULATE
+#define ATTN_PER_BLOCK(x) (x)
+#define ATTN_PER_BLOCK_TID() ((int)threadIdx.x)
+#else
+__device__ __forceinline__ long attn_opaque(long x) { asm volatile("" : "+s"(x)); return x; }
+__device__ __forceinline__ int attn_opaque_tid() { int x = threadIdx.x; asm volatile("" : "+v"(x)); return x; }
+#define ATTN_PER_BLOCK(x) attn_opaque(x)
+#define ATTN_PER_BLOCK_TID() attn_opaque_tid()
+#endif
+// key bias of the keys [k0, k0 + n_pad) in the exp2 domain; keys at or beyond nk get -inf
+__device__ __forceinline__ void stage_key_bias(float* kb, const AttnArgs& a, int b, int n_pad, int nk, int k0, int tid) {
+    for (int i = tid; i < n_pad; i += ATTN_THREADS)
+        kb[i] = k0 + i < nk ? (a.key_bias ? a.key_bias[(long)b * a.Nk + k0 + i] * LOG2E : 0.f) : -INFINITY;
+}
+
+template <int DH>
+__global__ __launch_bounds__(ATTN_THREADS, DH == 64 ? 4 : 2) void attn_fwd_stream_kernel(const AttnArgs a, int nqb) {
+    ANTMMF_DYN_LDS(char, smem);
+    constexpr int KB = ATTN_STREAM_KEYS(DH), SB = 128, NT = SB / 16, NCH = SB / 32, RB = 2 * DH, KM = DH / 32, DT = DH / 16;
+    char* Ks = smem;
+    char* Vs = smem + KB * RB;
+    float* kb = reinterpret_cast<float*>(Vs + KB * RB);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, grp = lane >> 4;
+    const int bh = blockIdx.x / nqb, b = bh / a.heads, h = bh % a.heads;
+    const int q0 = (blockIdx.x % nqb) * ATTN_STREAM_QB + wave * 16, qi = q0 + l15;
+    const bool wave_on = q0 < a.Nq;   // (a wave whose tile lies past the last query only stages)
+    const int qrow = qi < a.Nq ? qi : a.Nq - 1;
+    bf16x8_t qf[KM];
+    {
+        const bf16_t* qp = a.q + ((long)b * a.Nq + qrow) * a.ldq + h * DH + grp * 8;
+#pragma unroll
+        for (int j = 0; j < KM; ++j) qf[j] = load_frag_global(qp + 32 * j);
+    }
+    const float scale2 = a.scale * LOG2E;
+    const uint32_t dbase = (uint32_t)((((long)b * a.heads + h) * a.Nq + qrow) * a.Nk);
+    float m = -INFINITY, lsum = 0.f;   // running maximum (exp2 domain) of this lane's query; this lane's share of the running sum
+    f32x4_t o[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) o[dt] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    for (int k0 = 0; k0 < a.Nk; k0 += KB) {
+        const int nv = a.Nk - k0 < KB ? a.Nk - k0 : KB, npad = (nv + 31) & ~31;
+        const int tid = ATTN_PER_BLOCK_TID(), l15 = tid & 15, grp = (tid >> 4) & 3;
+        if (k0) __syncthreads();   // every wave is done with the previous block
+        stage_rows2<DH, KB>(Ks, a.k + ((long)b * a.Nk + k0) * a.ldk + h * DH, ATTN_PER_BLOCK(a.ldk), Vs, a.v + ((long)b * a.Nk + k0) * a.ldv + h * DH, ATTN_PER_BLOCK(a.ldv), nv, npad, tid);
+        stage_key_bias(kb, a, b, npad, a.Nk, k0, tid);
+        __syncthreads();
+        if (!wave_on) continue;
+        // one online-softmax step per SB keys of the block (the score registers of a step: 4 SB / 16 per lane)
+#pragma unroll 1
+        for (int s0 = 0; s0 < nv; s0 += SB) {
+            const char* Kb = Ks + s0 * RB;
+            const char* Vb = Vs + s0 * RB;
+            const int ns = nv - s0;   // valid keys from s0 on (>= SB: all of this step's)
+            float s[NT][4];
+            float mb = -INFINITY;
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                if (t % 3 == 0) LDS_FENCE();
+                if (16 * t < ns) {
+                    f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int j = 0; j < KM; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows<DH>(Kb, 16 * t + l15, 4 * j + grp), qf[j], acc, 0, 0, 0);
+                    const float4 bias = *reinterpret_cast<const float4*>(kb + s0 + 16 * t + 4 * grp);
+                    s[t][0] = acc[0] * scale2 + bias.x; s[t][1] = acc[1] * scale2 + bias.y;
+                    s[t][2] = acc[2] * scale2 + bias.z; s[t][3] = acc[3] * scale2 + bias.w;
+                    mb = fmaxf(mb, fmaxf(fmaxf(s[t][0], s[t][1]), fmaxf(s[t][2], s[t][3])));
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) s[t][r] = -INFINITY;
+                }
+            }
+            const float mn = fmaxf(m, grp_max(mb));
+            // nothing valid seen yet (mn = -inf: leading masked keys): keep the accumulators, every probability of the step is exp2(-inf - 0) = 0
+            const float alpha = mn == -INFINITY ? 1.f : EXP2F(m - mn), msub = mn == -INFINITY ? 0.f : mn;
+            m = mn;
+            lsum *= alpha;
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) o[dt] *= alpha;
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) { s[t][r] = EXP2F(s[t][r] - msub); lsum += s[t][r]; }
+            if (a.drop_thr) {   // drop probabilities (the softmax denominator keeps every key, as in the reference)
+#pragma unroll
+                for (int t = 0; t < NT; ++t)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (!DROPOUT_KEEP(dbase + k0 + s0 + 16 * t + 4 * grp + r, a.drop_seed, a.drop_thr)) s[t][r] = 0.f;
+            }
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) {
+                LDS_FENCE();
+                if (32 * c < ns) {
+                    const bf16x8_t pf = pack_frag(s[2 * c], s[2 * c + 1]);
+#pragma unroll
+                    for (int dt = 0; dt < DT; ++dt) o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tokens<DH>(Vb, c, dt, grp, l15), pf, o[dt], 0, 0, 0);
+                }
+            }
+        }
+    }
+    if (!wave_on) return;
+    const float sum = grp_sum(lsum);
+    float inv = sum > 0.f ? fast_rcp(sum) : 0.f;
+    if (a.drop_thr) inv *= a.drop_scale;
+    uint2 ow[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) ow[dt] = make_uint2(pack_bf2(o[dt][0] * inv, o[dt][1] * inv), pack_bf2(o[dt][2] * inv, o[dt][3] * inv));
+    const bool o_al16 = !(a.ldo & 7) && !((uintptr_t)a.o & 15);
+    store_rows_paired<DT>(a.o + ((long)b * a.Nq + qrow) * a.ldo + h * DH, ow, lane, grp, qi < a.Nq, o_al16);
+    if (grp == 0 && qi < a.Nq) a.lse[((long)b * a.heads + h) * a.Nq + qi] = sum > 0.f ? (m + LOG2F(sum)) * LN2 : -INFINITY;
+}
+
+template <int DH>
+__global__ __launch_bounds__(ATTN_THREADS, DH == 64 ? 4 : 2) void attn_bwd_dq_stream_kernel(const AttnArgs a, int nqb) {
+    ANTMMF_DYN_LDS(char, smem);
+    constexpr int KB = ATTN_STREAM_KEYS(DH), NCH = KB / 32, RB = 2 * DH, KM = DH / 32, DT = DH / 16;
+    char* Ks = smem;
+    char* Vs = smem + KB * RB;
+    float* kb = reinterpret_cast<float*>(Vs + KB * RB);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, grp = lane >> 4;
+    const int bh = blockIdx.x / nqb, b = bh / a.heads, h = bh % a.heads;
+    const int q0 = (blockIdx.x % nqb) * ATTN_STREAM_QB + wave * 16, qi = q0 + l15;
+    const bool wave_on = q0 < a.Nq;
+    const int qrow = qi < a.Nq ? qi : a.Nq - 1;
+    const long tok = (long)b * a.Nq + qrow;
+    bf16x8_t qf[KM], df[KM];
+    float dsum = 0.f;   // D_q = <dO[q], O[q]>: this lane covers dh 8g..8g+7 of every 32-wide slice
+    {
+        const bf16_t* qp = a.q + tok * a.ldq + h * DH + grp * 8;
+        const bf16_t* dop = a.d_o + tok * a.lddo + h * DH + grp * 8;
+        const bf16_t* op = a.o + tok * a.ldo + h * DH + grp * 8;
+#pragma unroll
+        for (int j = 0; j < KM; ++j) {
+            qf[j] = load_frag_global(qp + 32 * j);
+            df[j] = load_frag_global(dop + 32 * j);
+            union { bf16x8_t f; uint4 u; } d0;
+            d0.f = df[j];
+            const uint4 o0 = *reinterpret_cast<const uint4*>(op + 32 * j);
+            const uint32_t dw[4] = {d0.u.x, d0.u.y, d0.u.z, d0.u.w}, ow[4] = {o0.x, o0.y, o0.z, o0.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) dsum += bf_lo(dw[e]) * bf_lo(ow[e]) + bf_hi(dw[e]) * bf_hi(ow[e]);
+        }
+    }
+    dsum = grp_sum(dsum);
+    const float lse = a.lse[((long)b * a.heads + h) * a.Nq + qrow];
+    const float scale2 = a.scale * LOG2E, inv_scale2 = 1.0f / scale2;
+    // fully masked query (lse = -inf): subtracting +inf makes every exponent -inf and every p = 0 (see attn_bwd_dq64_kernel; the score accumulators start from -lse)
+    const float s_init = -(lse == -INFINITY ? INFINITY : lse * LOG2E) * inv_scale2;
+    const uint32_t dbase = (uint32_t)((((long)b * a.heads + h) * a.Nq + qrow) * a.Nk);
+    f32x4_t g[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) g[dt] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    for (int k0 = 0; k0 < a.Nk; k0 += KB) {
+        const int nv = a.Nk - k0 < KB ? a.Nk - k0 : KB, npad = (nv + 31) & ~31;
+        const int tid = ATTN_PER_BLOCK_TID(), l15 = tid & 15, grp = (tid >> 4) & 3;
+        if (k0) __syncthreads();
+        stage_rows2<DH, KB>(Ks, a.k + ((long)b * a.Nk + k0) * a.ldk + h * DH, ATTN_PER_BLOCK(a.ldk), Vs, a.v + ((long)b * a.Nk + k0) * a.ldv + h * DH, ATTN_PER_BLOCK(a.ldv), nv, npad, tid);
+        stage_key_bias(kb, a, b, npad, a.Nk, k0, tid);
+        __syncthreads();
+        if (!wave_on) continue;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            LDS_FENCE();
+            if (32 * c >= nv) continue;
+            float ds[2][4];
+#pragma unroll
+            for (int hh = 0; hh < 2; ++hh) {
+                const int t = 2 * c + hh;
+                if (16 * t >= nv) {   // a key tile of pure padding: dS = 0, no score work
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) ds[hh][r] = 0.f;
+                    continue;
+                }
+                f32x4_t sa = {s_init, s_init, s_init, s_init}, da = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int j = 0; j < KM; ++j) sa = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows<DH>(Ks, 16 * t + l15, 4 * j + grp), qf[j], sa, 0, 0, 0);
+#pragma unroll
+                for (int j = 0; j < KM; ++j) da = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows<DH>(Vs, 16 * t + l15, 4 * j + grp), df[j], da, 0, 0, 0);
+                const float4 bias = *reinterpret_cast<const float4*>(kb + 16 * t + 4 * grp);
+                const float bb[4] = {bias.x, bias.y, bias.z, bias.w};
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float p = EXP2F(__builtin_fmaf(sa[r], scale2, bb[r]));  // masked key: bias = -inf -> p = 0
+                    float dp = da[r];
+                    if (a.drop_thr) dp = DROPOUT_KEEP(dbase + k0 + 16 * t + 4 * grp + r, a.drop_seed, a.drop_thr) ? dp * a.drop_scale : 0.f;
+                    ds[hh][r] = p * (dp - dsum);
+                }
+            }
+            const bf16x8_t dsf = pack_frag(ds[0], ds[1]);
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) g[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tokens<DH>(Ks, c, dt, grp, l15), dsf, g[dt], 0, 0, 0);
+        }
+    }
+    if (!wave_on) return;
+    uint2 gw[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) gw[dt] = make_uint2(pack_bf2(g[dt][0] * a.scale, g[dt][1] * a.scale), pack_bf2(g[dt][2] * a.scale, g[dt][3] * a.scale));
+    const bool dq_al16 = !(a.lddq & 7) && !((uintptr_t)a.dq & 15);
+    store_rows_paired<DT>(a.dq + tok * a.lddq + h * DH, gw, lane, grp, qi < a.Nq, dq_al16);
+}
+
+template <int DH>
+__global__ __launch_bounds__(ATTN_THREADS, DH == 64 ? 4 : 2) void attn_bwd_dkv_stream_kernel(const AttnArgs a, int nkb) {
+    ANTMMF_DYN_LDS(char, smem);
+    constexpr int QBS = ATTN_STREAM_KEYS(DH), RB = 2 * DH, KM = DH / 32, DT = DH / 16, NS = DH / 8;   // QBS: queries per staged block
+    char* Qs = smem;
+    char* Ds = Qs + QBS * RB;
+    float* lse_s = reinterpret_cast<float*>(Ds + QBS * RB);
+    float* dsum_s = lse_s + QBS;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, grp = lane >> 4;
+    const int bh = blockIdx.x / nkb, b = bh / a.heads, h = bh % a.heads;
+    const int kt0 = (blockIdx.x % nkb) * ATTN_STREAM_QB + wave * 16, ki = kt0 + l15;
+    const bool wave_on = kt0 < a.Nk;
+    const int krow = ki < a.Nk ? ki : a.Nk - 1;
+    const bf16_t* qbase = a.q + (long)b * a.Nq * a.ldq + h * DH;
+    const bf16_t* dobase = a.d_o + (long)b * a.Nq * a.lddo + h * DH;
+    const bf16_t* obase = a.o + (long)b * a.Nq * a.ldo + h * DH;
+    bf16x8_t kf[KM], vf[KM];
+    {
+        const bf16_t* kp = a.k + ((long)b * a.Nk + krow) * a.ldk + h * DH + grp * 8;
+        const bf16_t* vp = a.v + ((long)b * a.Nk + krow) * a.ldv + h * DH + grp * 8;
+#pragma unroll
+        for (int j = 0; j < KM; ++j) { kf[j] = load_frag_global(kp + 32 * j); vf[j] = load_frag_global(vp + 32 * j); }
+    }
+    const float kbias = ki < a.Nk ? (a.key_bias ? a.key_bias[(long)b * a.Nk + ki] * LOG2E : 0.f) : -INFINITY;
+    const float scale2 = a.scale * LOG2E;
+    f32x4_t dk[DT], dv[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) { dk[dt] = (f32x4_t){0.f, 0.f, 0.f, 0.f}; dv[dt] = (f32x4_t){0.f, 0.f, 0.f, 0.f}; }
+    for (int qb0 = 0; qb0 < a.Nq; qb0 += QBS) {
+        const int nv = a.Nq - qb0 < QBS ? a.Nq - qb0 : QBS, npad = (nv + 31) & ~31;
+        const int tid = ATTN_PER_BLOCK_TID(), l15 = tid & 15, grp = (tid >> 4) & 3;
+        if (qb0) __syncthreads();
+        const long ldq = ATTN_PER_BLOCK(a.ldq), lddo = ATTN_PER_BLOCK(a.lddo), ldo = ATTN_PER_BLOCK(a.ldo);
+        stage_rows2<DH, QBS>(Qs, qbase + (long)qb0 * ldq, ldq, Ds, dobase + (long)qb0 * lddo, lddo, nv, npad, tid);
+        for (int i = tid; i < npad; i += ATTN_THREADS) {
+            float d = 0.f, l = INFINITY;  // padding queries: p = 0
+            if (i < nv) {
+                l = a.lse[((long)b * a.heads + h) * a.Nq + qb0 + i];
+                l = l == -INFINITY ? INFINITY : l / a.scale;  // lse in units of the raw score, negated below: what the score accumulators start from (fully masked query: p = 0)
+#pragma unroll
+                for (int v = 0; v < NS; ++v) {
+                    float x[8], y[8];
+                    ld8<bf16_t>(dobase + (long)(qb0 + i) * lddo + v * 8, x);
+                    ld8<bf16_t>(obase + (long)(qb0 + i) * ldo + v * 8, y);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) d += x[e] * y[e];
+                }
+            }
+            lse_s[i] = -l;
+            dsum_s[i] = -d;
+        }
+        __syncthreads();
+        if (!wave_on) continue;
+        const int nqc = npad >> 5;
+        for (int c = 0; c < nqc; ++c) {
+            float p[2][4], ds[2][4];
+#pragma unroll
+            for (int hh = 0; hh < 2; ++hh) {
+                const int q0 = 32 * c + 16 * hh;
+                if (q0 >= nv) {   // a 16-query tile of pure padding: p = dS = 0, no score work
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) { p[hh][r] = 0.f; ds[hh][r] = 0.f; }
+                    continue;
+                }
+                // lane holds (key = l15, q = qb0 + q0 + 4g + r); accumulators start from -lse (raw-score units), see attn_bwd_dkv_kernel
+                const float4 l4 = *reinterpret_cast<const float4*>(lse_s + q0 + 4 * grp);
+                const float4 d4 = *reinterpret_cast<const float4*>(dsum_s + q0 + 4 * grp);
+                const float dd[4] = {d4.x, d4.y, d4.z, d4.w};
+                f32x4_t sa = {l4.x, l4.y, l4.z, l4.w}, da = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int j = 0; j < KM; ++j) sa = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows<DH>(Qs, q0 + l15, 4 * j + grp), kf[j], sa, 0, 0, 0);
+#pragma unroll
+                for (int j = 0; j < KM; ++j) da = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows<DH>(Ds, q0 + l15, 4 * j + grp), vf[j], da, 0, 0, 0);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float pr = EXP2F(__builtin_fmaf(sa[r], scale2, kbias));  // masked / padding key or query: -inf -> 0
+                    float pd = pr, dp = da[r];
+                    if (a.drop_thr) {
+                        const int qq = qb0 + q0 + 4 * grp + r;
+                        const bool keep = DROPOUT_KEEP((uint32_t)((((long)b * a.heads + h) * a.Nq + (qq < a.Nq ? qq : a.Nq - 1)) * a.Nk) + krow, a.drop_seed, a.drop_thr);
+                        pd = keep ? pr * a.drop_scale : 0.f;
+                        dp = keep ? dp * a.drop_scale : 0.f;
+                    }
+                    p[hh][r] = pd;                     // dV uses the dropped probabilities
+                    ds[hh][r] = pr * (dp + dd[r]);     // dS uses the softmax probabilities
+                }
+            }
+            const bf16x8_t pf = pack_frag(p[0], p[1]), dsf = pack_frag(ds[0], ds[1]);
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) {
+                dv[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tokens<DH>(Ds, c, dt, grp, l15), pf, dv[dt], 0, 0, 0);
+                dk[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tokens<DH>(Qs, c, dt, grp, l15), dsf, dk[dt], 0, 0, 0);
+            }
+        }
+    }
+    if (!wave_on) return;
+    uint2 vw[DT], kw[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) {
+        vw[dt] = make_uint2(pack_bf2(dv[dt][0], dv[dt][1]), pack_bf2(dv[dt][2], dv[dt][3]));
+        kw[dt] = make_uint2(pack_bf2(dk[dt][0] * a.scale, dk[dt][1] * a.scale), pack_bf2(dk[dt][2] * a.scale, dk[dt][3] * a.scale));
+    }
+    const bool dkv_al16 = !(a.lddk & 7) && !(a.lddv & 7) && !((uintptr_t)a.dk & 15) && !((uintptr_t)a.dv & 15);
+    store_rows_paired<DT>(a.dv + ((long)b * a.Nk + krow) * a.lddv + h * DH, vw, lane, grp, ki < a.Nk, dkv_al16);
+    store_rows_paired<DT>(a.dk + ((long)b * a.Nk + krow) * a.lddk + h * DH, kw, lane, grp, ki < a.Nk, dkv_al16);
+}
+
 // ---- backward in ONE kernel (head size 64, 32 < Nk <= 272, no dropout: every tower of the contrastive step) --------------------------------------------------
 // Why: at these lengths the backward is closer to its HBM floor than to the MFMA peak -- the two kernels above read Q, K, V, dO, O TWICE and form the
 // scores, dP and the exponentials twice (13 tensor passes, 14 flop units, 2 exponentials per score); one kernel needs 8 passes, 10 units, 1 exponential.
@@ -1451,13 +1783,24 @@ static void set_lds(K kern, size_t bytes) { (void)hipFuncSetAttribute(reinterpre
 #define ATTN_BWDF(P, A, STREAM, NKS, HASE, FULL, NQC, PERS, ABL, EARLY, SUMS)   /* the one-kernel backward of plan P */ \
     ATTN_LAUNCH((attn_bwd_fused64_kernel<NKS, HASE, FULL, NQC, PERS, ABL, EARLY, SUMS>), (P).grid, (P).lds, STREAM, A, (P).nqp, (A).B * (A).heads)
 
-static bool attn_shape_ok(int dh, int B, int heads, int Nq, int Nk) { return (dh == 64 || dh == 128) && B > 0 && heads > 0 && Nq > 0 && Nk > 0 && Nq <= 288 && Nk <= 288; }
+#define ATTN_WHOLE_ROW_MAX_TOKENS 288
+static bool attn_dims_ok(int dh, int B, int heads, int Nq, int Nk) { return (dh == 64 || dh == 128) && B > 0 && heads > 0 && Nq > 0 && Nk > 0; }
+// the whole-row kernels -- and everything that exists in whole-row form only: the packed entry points, the token sums, the probability maps, the key importance
+static bool attn_shape_ok(int dh, int B, int heads, int Nq, int Nk) { return attn_dims_ok(dh, B, heads, Nq, Nk) && Nq <= ATTN_WHOLE_ROW_MAX_TOKENS && Nk <= ATTN_WHOLE_ROW_MAX_TOKENS; }
+// the streamed kernels: every other shape up to 4096 x 4096 (one side may be short: cross-length calls)
+static bool attn_stream_shape_ok(int dh, int B, int heads, int Nq, int Nk) {
+    return attn_dims_ok(dh, B, heads, Nq, Nk) && !attn_shape_ok(dh, B, heads, Nq, Nk) && Nq <= ATTN_STREAM_MAX_TOKENS && Nk <= ATTN_STREAM_MAX_TOKENS;
+}
 // 32-key chunks the whole-row kernels (forward, the two-kernel backward's dQ kernel) are instantiated for
 static int attn_key_chunks(int Nk) { const int nch = (Nk + 31) / 32; return nch <= 1 ? 1 : nch <= 3 ? 3 : nch <= 7 ? 7 : 9; }
-// forward: the NCH of attn_fwd_kernel, 0 = not served (the packed form: head size 64)
-static int attn_fwd_plan(int dh, int B, int heads, int Nq, int Nk, bool packed) { return attn_shape_ok(dh, B, heads, Nq, Nk) && !(packed && dh != 64) ? attn_key_chunks(Nk) : 0; }
+// forward: the NCH of attn_fwd_kernel, ATTN_FWD_STREAM = attn_fwd_stream_kernel, 0 = not served (the packed form: head size 64, whole rows)
+#define ATTN_FWD_STREAM (-1)
+static int attn_fwd_plan(int dh, int B, int heads, int Nq, int Nk, bool packed) {
+    if (attn_shape_ok(dh, B, heads, Nq, Nk)) return !(packed && dh != 64) ? attn_key_chunks(Nk) : 0;
+    return !packed && attn_stream_shape_ok(dh, B, heads, Nq, Nk) ? ATTN_FWD_STREAM : 0;
+}
 
-enum AttnBwdForm { ATTN_BWD_NONE = 0 /* ANTMMF_EINVAL */, ATTN_BWD_TWO_KERNEL, ATTN_BWD_FUSED_PER_ITEM, ATTN_BWD_FUSED_PERSIST };
+enum AttnBwdForm { ATTN_BWD_NONE = 0 /* ANTMMF_EINVAL */, ATTN_BWD_TWO_KERNEL, ATTN_BWD_FUSED_PER_ITEM, ATTN_BWD_FUSED_PERSIST, ATTN_BWD_STREAM };
 struct AttnBwdPlan {
     AttnBwdForm form;
     int nch;                   // two kernels: NCH of the dQ kernel
@@ -1465,8 +1808,10 @@ struct AttnBwdPlan {
     bool early;                // one kernel: the double-buffered persistent form (the only one that reads an item table)
     int nqp;                   // queries padded to 32
     size_t lds;                // of the fused kernel / of the dQ kernel
-    unsigned grid;
+    unsigned grid;             // (streamed: of the dQ kernel)
+    int nqb, nkb;              // streamed: blocks of ATTN_STREAM_QB queries / keys per (b, h)
 };
+static size_t attn_stream_lds_bytes(int dh) { return (size_t)ATTN_STREAM_KEYS(dh) * (4 * dh + 8); }   // two token tiles + two fp32 rows (the forward and dQ use one of them)
 // the two-kernel form of any served shape (what the plan falls back to, and what the lab library's A/B switch forces)
 static void attn_bwd_two_kernel(AttnBwdPlan& p, int dh, int B, int heads, int Nk) {
     p.form = ATTN_BWD_TWO_KERNEL; p.nch = attn_key_chunks(Nk); p.lds = (size_t)(32 * p.nch) * (4 * dh + 4); p.grid = (unsigned)(B * heads);
@@ -1474,7 +1819,13 @@ static void attn_bwd_two_kernel(AttnBwdPlan& p, int dh, int B, int heads, int Nk
 // sums: 0 none, 1 dQ | dK | dV, 2 dQ | dK.  persist_wgs: workgroups of the persistent form (one per CU walking the items)
 static AttnBwdPlan attn_bwd_plan(int dh, int B, int heads, int Nq, int Nk, bool dropout, bool packed, int sums, unsigned persist_wgs) {
     AttnBwdPlan p{};
-    if (!attn_shape_ok(dh, B, heads, Nq, Nk)) return p;
+    if (!attn_shape_ok(dh, B, heads, Nq, Nk)) {
+        if (sums || packed || !attn_stream_shape_ok(dh, B, heads, Nq, Nk)) return p;   // (neither exists in the streamed form)
+        p.form = ATTN_BWD_STREAM; p.lds = attn_stream_lds_bytes(dh);
+        p.nqb = (Nq + ATTN_STREAM_QB - 1) / ATTN_STREAM_QB; p.nkb = (Nk + ATTN_STREAM_QB - 1) / ATTN_STREAM_QB;
+        p.grid = (unsigned)(B * heads * p.nqb);
+        return p;
+    }
     const size_t lds_max = 160 * 1024;
     const unsigned n_items = (unsigned)(B * heads);
     p.nqp = ((Nq + 31) / 32) * 32;
@@ -1566,11 +1917,19 @@ template <int DH>
 static int attn_fwd_launch(AttnArgs a, hipStream_t stream) {
     const int nch = attn_fwd_plan(DH, a.B, a.heads, a.Nq, a.Nk, a.items != nullptr);
 #ifdef ANTMMF_LAB
-    if (nch && attn_fwd_lab<DH>(a, stream)) return antmmf_check_launch();
+    if (nch > 0 && attn_fwd_lab<DH>(a, stream)) return antmmf_check_launch();
 #endif
 #define FWD(N) do { const size_t lds = (size_t)(32 * N) * (4 * DH) + (32 * N) * 4; \
         if (a.drop_thr) ATTN_LAUNCH((attn_fwd_kernel<N, true, DH>), a.B * a.heads, lds, stream, a); else ATTN_LAUNCH((attn_fwd_kernel<N, false, DH>), a.B * a.heads, lds, stream, a); } while (0)
-    switch (nch) { case 1: FWD(1); break; case 3: FWD(3); break; case 7: FWD(7); break; case 9: FWD(9); break; default: return ANTMMF_EINVAL; }
+    switch (nch) {
+        case 1: FWD(1); break; case 3: FWD(3); break; case 7: FWD(7); break; case 9: FWD(9); break;
+        case ATTN_FWD_STREAM: {
+            const int nqb = (a.Nq + ATTN_STREAM_QB - 1) / ATTN_STREAM_QB;
+            ATTN_LAUNCH((attn_fwd_stream_kernel<DH>), a.B * a.heads * nqb, attn_stream_lds_bytes(DH), stream, a, nqb);
+            break;
+        }
+        default: return ANTMMF_EINVAL;
+    }
 #undef FWD
     return antmmf_check_launch();
 }
@@ -1583,6 +1942,13 @@ static int attn_bwd_launch(const AttnArgs& a, hipStream_t stream) {
     if (attn_bwd_lab(p, DH, a, sums, stream)) return antmmf_check_launch();
 #endif
     if (p.form == ATTN_BWD_NONE) return ANTMMF_EINVAL;
+    if (p.form == ATTN_BWD_STREAM) {
+        ATTN_LAUNCH((attn_bwd_dq_stream_kernel<DH>), p.grid, p.lds, stream, a, p.nqb);
+        const int rc = antmmf_check_launch();
+        if (rc) return rc;
+        ATTN_LAUNCH((attn_bwd_dkv_stream_kernel<DH>), (unsigned)(a.B * a.heads * p.nkb), p.lds, stream, a, p.nkb);
+        return antmmf_check_launch();
+    }
     if constexpr (DH == 64) {
         if (p.form != ATTN_BWD_TWO_KERNEL) {
 #define BWDF3(NKS, HASE, FULL, NQC, PERS, EARLY) do { if (sums == 1) ATTN_BWDF(p, a, stream, NKS, HASE, FULL, NQC, PERS, 0, EARLY, 1); else if (sums) ATTN_BWDF(p, a, stream, NKS, HASE, FULL, NQC, PERS, 0, EARLY, 2); \
@@ -1653,6 +2019,14 @@ extern "C" int antmmf_attention_bwd_hd(const void* q, const void* k, const void*
     return attn_operands_ok(a, true) ? attn_bwd(a, head_dim, stream) : ANTMMF_EINVAL;
 }
 
+// Host-only: the longest row of the whole-row kernels (also the limit of the packed entry points, the token sums, the probability maps and the key importance)
+// and the longest row antmmf_attention_fwd[_hd] / antmmf_attention_bwd[_hd] serve at all (the streamed kernels)
+extern "C" int antmmf_attention_limits(int* whole_row, int* streamed) {
+    if (whole_row) *whole_row = ATTN_WHOLE_ROW_MAX_TOKENS;
+    if (streamed) *streamed = ATTN_STREAM_MAX_TOKENS;
+    return ANTMMF_OK;
+}
+
 // head size 64: the entry points every tower of the contrastive path uses
 extern "C" int antmmf_attention_fwd(const void* q, const void* k, const void* v, const float* key_bias, void* o, float* lse,
                                     int B, int heads, int Nq, int Nk, long ldq, long ldk, long ldv, long ldo, float scale,
@@ -1720,96 +2094,21 @@ extern "C" int antmmf_attention_bwd_sums_packed(const void* q, const void* k, co
 
 // ---- key importance: column sums of the attention probabilities --------------------------------------------------------------------------------
 // out[b][k] += weight * sum_h sum_q P_drop[b][h][q][k]  -- what the reference does with the attention MAPS it asks the text tower for in training
-// (`output_attentions=True`, prj/base_vtp/roi_univl/univl/model/univl_video_base.py:131-143: cat over layers of the head mean, summed over layers and
-// queries -> words_importance).  The maps are not written for this (only on request: attn_probs_kernel below); the probabilities are rebuilt from Q, K and the forward's log-sum-exp exactly as the backward
-// kernels do (same dropout mask: HF's BertSelfAttention returns the probabilities AFTER dropout), summed over the queries in registers, over the 16 query
-// lanes by DPP, over the waves in LDS, and leave as one atomic add per (b, h, key).  Head size 64.
-template <int NCH, bool DROP>
-__global__ __launch_bounds__(ATTN_THREADS, 2) void attn_key_importance_kernel(const AttnArgs a, float* __restrict__ out, float weight) {
-    ANTMMF_DYN_LDS(char, smem);
-    constexpr int NKP = 32 * NCH, NT = 2 * NCH;
-    char* Ks = smem;
-    float* kb = reinterpret_cast<float*>(Ks + NKP * 128);
-    float* colsum = kb + NKP;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, grp = lane >> 4;
-    const int b = blockIdx.x / a.heads, h = blockIdx.x % a.heads;
-    stage_rows<64, NKP>(Ks, a.k + (long)b * a.Nk * a.ldk + h * 64, a.ldk, a.Nk, NKP);
-    stage_key_bias(kb, a, b, NKP);
-    for (int i = threadIdx.x; i < NKP; i += ATTN_THREADS) colsum[i] = 0.f;
-    __syncthreads();
-    const float scale2 = a.scale * LOG2E;
-    const int nqt = (a.Nq + 15) >> 4;
-    float part[NT][4];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) part[t][r] = 0.f;
-    for (int qt = wave; qt < nqt; qt += ATTN_THREADS / 64) {
-        const int qi = qt * 16 + l15;
-        const int qrow = qi < a.Nq ? qi : a.Nq - 1;
-        const bf16_t* qp = a.q + ((long)b * a.Nq + qrow) * a.ldq + h * 64 + grp * 8;
-        const bf16x8_t qf0 = load_frag_global(qp), qf1 = load_frag_global(qp + 32);
-        const float lse = a.lse[((long)b * a.heads + h) * a.Nq + qrow];
-        // padding queries and fully masked ones (lse = -inf) contribute nothing: subtracting +inf makes every exponent -inf
-        const float lse2 = (qi >= a.Nq || lse == -INFINITY) ? INFINITY : lse * LOG2E;
-        const uint32_t dbase = (uint32_t)((((long)b * a.heads + h) * a.Nq + qrow) * a.Nk);
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            if (t % 3 == 0) LDS_FENCE();
-            f32x4_t sa = {0.f, 0.f, 0.f, 0.f};
-            sa = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows<64>(Ks, 16 * t + l15, grp), qf0, sa, 0, 0, 0);
-            sa = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows<64>(Ks, 16 * t + l15, 4 + grp), qf1, sa, 0, 0, 0);
-            const float4 bias = *reinterpret_cast<const float4*>(kb + 16 * t + 4 * grp);
-            const float bb[4] = {bias.x, bias.y, bias.z, bias.w};
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float pr = EXP2F(sa[r] * scale2 + bb[r] - lse2);
-                if (DROP) pr = DROPOUT_KEEP(dbase + 16 * t + 4 * grp + r, a.drop_seed, a.drop_thr) ? pr * a.drop_scale : 0.f;
-                part[t][r] += pr;
-            }
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float v = row16_sum(part[t][r]);   // over the wave's 16 query lanes
-            if (l15 == 0) atomicAdd(colsum + 16 * t + 4 * grp + r, v);
-        }
-    __syncthreads();
-    for (int i = threadIdx.x; i < a.Nk; i += ATTN_THREADS) atomicAdd(out + (long)b * a.Nk + i, colsum[i] * weight);
-}
-
-extern "C" int antmmf_attention_key_importance(const void* q, const void* k, const float* key_bias, const float* lse, float* out, int B, int heads, int Nq, int Nk,
-                                               long ldq, long ldk, float scale, float dropout_p, uint64_t dropout_seed, float weight, hipStream_t stream) {
-    AttnArgs a{};
-    if (!(dropout_p >= 0.f && dropout_p < 1.f)) return ANTMMF_EINVAL;
-    a.drop_thr = dropout_threshold(dropout_p); a.drop_scale = 1.0f / (1.0f - dropout_p); a.drop_seed = dropout_seed;
-    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.key_bias = key_bias; a.lse = const_cast<float*>(lse);
-    a.ldq = ldq; a.ldk = ldk; a.B = B; a.heads = heads; a.Nq = Nq; a.Nk = Nk; a.scale = scale;
-    if (!q || !k || !lse || !out || B <= 0 || heads <= 0 || Nq <= 0 || Nk <= 0 || Nk > 288 || Nq > 288 || (ldq & 7) || (ldk & 7)) return ANTMMF_EINVAL;
-    const int nch = (Nk + 31) / 32;
-    const dim3 grid((unsigned)(B * heads)), block(ATTN_THREADS);
-#define KIMP(N) do { const size_t lds = (size_t)(32 * N) * 128 + (32 * N) * 8; \
-        if (a.drop_thr) { set_lds(attn_key_importance_kernel<N, true>, lds); hipLaunchKernelGGL((attn_key_importance_kernel<N, true>), grid, block, lds, stream, a, out, weight); } \
-        else { set_lds(attn_key_importance_kernel<N, false>, lds); hipLaunchKernelGGL((attn_key_importance_kernel<N, false>), grid, block, lds, stream, a, out, weight); } } while (0)
-    if (nch <= 1) KIMP(1); else if (nch <= 3) KIMP(3); else if (nch <= 7) KIMP(7); else KIMP(9);
-#undef KIMP
-    return antmmf_check_launch();
-}
+// (`output_attentions=True`, univl_video_base.py:131-143 -> words_importance; post-dropout probabilities, as HF returns them).
+// The kernel is attn_probs_kernel below with probs = nullptr (one instantiation for every key count, both head sizes, with or without dropout); the entry point follows it.
 
 // ---- attention probability maps, on request -----------------------------------------------------------------------------------------------------
 // probs[b][h][q][k] = P_drop (fp32, dense [B, heads, Nq, Nk]) and / or importance[b][k] += weight * sum_h sum_q P_drop -- the tensors the reference hands back
 // from BertSelfAttention / BertEncoder with `output_attentions=True` (modeling_bert.py:144-161, 283-314: one map per layer, AFTER dropout, as HuggingFace does),
 // from BertBiAttention(visualization=True) (vilbert.py:360-414: `attn1` / `attn2`), and their reduction words_importance (univl_video_base.py:131-143).  The
 // forward and backward kernels never write them; this sibling rebuilds P = exp2(scale log2e q.k + key_bias log2e - lse log2e) from Q, K and the forward's
-// log-sum-exp exactly as attn_key_importance_kernel above does (K staged once into the swizzled LDS tile, scores transposed, 16-query tiles per wave, the same
+// log-sum-exp exactly as the backward kernels do (K staged once into the swizzled LDS tile, scores transposed, 16-query tiles per wave, the same
 // DROPOUT_KEEP counter -- so the mask is the forward's), and runs only when a caller asks for the maps.
 // ONE instantiation serves everything: head size (64 / 128), dropout, the number of 16-key tiles and the choice of outputs are run-time, wave-uniform values.  The
 // key tiles are a run-time loop whose four probabilities per lane are used and dropped (no per-thread array is indexed by a run-time value: no scratch): stored
 // per lane -- a lane holds 4 consecutive keys of one query, 16 B where the element index is a multiple of 4 and all four keys exist (Nk is often odd: 77, 257),
 // scalar stores otherwise -- and, for the importance, reduced over the 16 query lanes and added into the LDS column strip.
-// Deviation from the reference, the rule of attn_key_importance_kernel: a fully masked query row (lse = -inf) is a row of ZEROS (the reference's softmax gives NaN
+// Deviation from the reference, the rule of the key importance: a fully masked query row (lse = -inf) is a row of ZEROS (the reference's softmax gives NaN
 // under -inf masks and a uniform row under -10000 ones); query rows at or beyond Nq do not exist.  Every element of a valid row is written, zeros included.
 template <int DH>
 __device__ __forceinline__ void attn_probs_body(const AttnArgs& a, float* __restrict__ probs, float* __restrict__ importance, float weight, int nkt, char* smem) {
@@ -1911,5 +2210,21 @@ extern "C" int antmmf_attention_probs(const void* q, const void* k, const float*
     const size_t lds = (size_t)(16 * nkt) * (2 * head_dim + 8);   // K tile, key bias, column sums: 74.25 KiB at 288 keys of head size 128 (two workgroups per CU)
     set_lds(attn_probs_kernel, lds);
     hipLaunchKernelGGL(attn_probs_kernel, dim3((unsigned)(B * heads)), dim3(ATTN_THREADS), lds, stream, a, probs, importance, weight, head_dim, nkt);
+    return antmmf_check_launch();
+}
+
+// key importance alone (head size 64; see the section above): attn_probs_kernel without the maps
+extern "C" int antmmf_attention_key_importance(const void* q, const void* k, const float* key_bias, const float* lse, float* out, int B, int heads, int Nq, int Nk,
+                                               long ldq, long ldk, float scale, float dropout_p, uint64_t dropout_seed, float weight, hipStream_t stream) {
+    AttnArgs a{};
+    if (!(dropout_p >= 0.f && dropout_p < 1.f)) return ANTMMF_EINVAL;
+    a.drop_thr = dropout_threshold(dropout_p); a.drop_scale = 1.0f / (1.0f - dropout_p); a.drop_seed = dropout_seed;
+    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.key_bias = key_bias; a.lse = const_cast<float*>(lse);
+    a.ldq = ldq; a.ldk = ldk; a.B = B; a.heads = heads; a.Nq = Nq; a.Nk = Nk; a.scale = scale;
+    if (!q || !k || !lse || !out || B <= 0 || heads <= 0 || Nq <= 0 || Nk <= 0 || Nk > 288 || Nq > 288 || (ldq & 7) || (ldk & 7)) return ANTMMF_EINVAL;
+    const int nkt = (Nk + 15) / 16;
+    const size_t lds = (size_t)(16 * nkt) * (2 * 64 + 8);
+    set_lds(attn_probs_kernel, lds);
+    hipLaunchKernelGGL(attn_probs_kernel, dim3((unsigned)(B * heads)), dim3(ATTN_THREADS), lds, stream, a, (float*)nullptr, out, weight, 64, nkt);
     return antmmf_check_launch();
 }

@@ -200,7 +200,13 @@ int antmmf_gemm_wgrad_bf16_seg(const void* dY, const void* X, float* const* dW, 
                                int64_t ld_dy, int64_t ld_x, int64_t ld_dw, int split_k_hint, float* workspace, int64_t workspace_bytes,
                                antmmf_stream_t stream);
 
-/* ---- fused multi-head attention, head_dim = 64, bf16, Nk <= 288 (whole key row in LDS):
+/* Rows the attention entry points serve, in tokens (queries and keys alike; host only, no GPU call): *whole_row = 288, the whole-row kernels -- the only form of
+ * the packed entry points, the token sums, antmmf_attention_probs and antmmf_attention_key_importance; *streamed = 4096, the longest row of antmmf_attention_fwd[_hd]
+ * and antmmf_attention_bwd[_hd] (rows beyond 288 on either side run in kernels that stream the other side through LDS in blocks; with or without dropout and key
+ * bias, both head sizes, no atomics).  Beyond *streamed: ANTMMF_EINVAL.  Either pointer may be NULL. */
+int antmmf_attention_limits(int* whole_row, int* streamed);
+
+/* ---- fused multi-head attention, head_dim = 64, bf16, Nq, Nk <= 4096 (<= 288: whole key row in LDS; longer: streamed, see above):
  *   O[b,q,h,:] = softmax_k( scale * <Q[b,q,h,:], K[b,k,h,:]> + key_bias[b,k] ) V[b,k,h,:]
  * element (b, n, h, e) of Q lives at q + (b*Nq + n)*ldq + h*64 + e (K, V with Nk / ldk / ldv; O with ldo), so a packed
  * [B, N, 3, heads, 64] projection output is addressed with ld = 3*heads*64 and no copy.  key_bias [B, Nk] fp32 (nullable):
@@ -219,7 +225,7 @@ int antmmf_attention_bwd(const void* q, const void* k, const void* v, const floa
                          int Nk, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t lddo, int64_t lddq,
                          int64_t lddk, int64_t lddv, float scale, float dropout_p, uint64_t dropout_seed,
                          antmmf_stream_t stream);
-/* Key importance (head size 64): out[b][k] += weight * sum over heads and queries of the (post-dropout) attention probabilities, rebuilt from q, k and the
+/* Key importance (head size 64, at most 288 queries and keys; served by the probability-map kernel of antmmf_attention_probs without its map output): out[b][k] += weight * sum over heads and queries of the (post-dropout) attention probabilities, rebuilt from q, k and the
  * forward's lse -- the reduction the reference applies to the attention MAPS of `output_attentions=True` (words_importance,
  * prj/base_vtp/roi_univl/univl/model/univl_video_base.py:131-143; maps from modeling_bert.py:144-172).  out [B, Nk] fp32 is accumulated into (atomics). */
 int antmmf_attention_key_importance(const void* q, const void* k, const float* key_bias, const float* lse, float* out, int B, int heads,
