@@ -183,6 +183,101 @@ __device__ __forceinline__ void stage_key_bias(float* kb, const AttnArgs& a, int
         kb[i] = i < nk ? (a.key_bias ? a.key_bias[(long)b * a.Nk + i] * LOG2E : 0.f) : -INFINITY;
 }
 __device__ __forceinline__ void stage_key_bias(float* kb, const AttnArgs& a, int b, int n_pad) { stage_key_bias(kb, a, b, n_pad, a.Nk); }
+// one output fragment (4 consecutive head-dim values of one token) times a factor, as bf16
+__device__ __forceinline__ uint2 pack_acc(const f32x4_t& acc, float f) { return make_uint2(pack_bf2(acc[0] * f, acc[1] * f), pack_bf2(acc[2] * f, acc[3] * f)); }
+
+// ---- the tile math of the two-kernel backward and its streamed forms -----------------------------------------------------------------------------------
+// -lse and -D_q (D_q = <dO[q], O[q]>) are what the score / dP accumulators of a tile START from: z = s scale2 + bias - lse2 becomes ONE fused multiply-add behind the
+// MFMAs and, where D is in the accumulator, dS = p dP' one multiply -- 6.5 instead of 8.5 VALU slots per score.  A fully masked query (lse = -inf) starts at -inf
+// (+inf is subtracted) and stays there: every exponent is -inf and p = 0 without per-element selects.  Padding queries are staged the same way.
+// Where D sits differs and is kept as it was measured: the whole-row kernels without dropout start dP from -D; with dropout the keep-and-scale comes between the
+// contraction and D, so dP starts from 0 and -D is added behind it; the streamed kernels (dropout is a run-time value there) always start from 0.
+
+// this lane's share of D_q from the dO fragments it holds (dh 8g..8g+7 of every 32-wide slice) and the same slices of O at `op`; grp_sum closes it
+template <int KM>
+__device__ __forceinline__ float dot_do_o(const bf16x8_t (&df)[KM], const bf16_t* op) {
+    float dsum = 0.f;
+#pragma unroll
+    for (int j = 0; j < KM; ++j) {
+        union { bf16x8_t f; uint4 u; } d0;
+        d0.f = df[j];
+        const uint4 o0 = *reinterpret_cast<const uint4*>(op + 32 * j);
+        const uint32_t dw[4] = {d0.u.x, d0.u.y, d0.u.z, d0.u.w}, ow[4] = {o0.x, o0.y, o0.z, o0.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) dsum += bf_lo(dw[e]) * bf_lo(ow[e]) + bf_hi(dw[e]) * bf_hi(ow[e]);
+    }
+    return dsum;
+}
+// dS of key tile t of the K / V tiles in LDS for the wave's 16 queries (lane: query l15, keys 16 t + 4 grp + r).  The accumulators start from s_init / d_init, d_sub
+// is subtracted behind the dropout (a literal +0.f folds away: x - (+0) is x for every x); dctr: the dropout counter of r = 0.
+template <int DH>
+__device__ __forceinline__ void bwd_q_tile_ds(float (&ds)[4], const char* Ks, const char* Vs, const float* kb, int t, const bf16x8_t (&qf)[DH / 32], const bf16x8_t (&df)[DH / 32],
+                                              float s_init, float d_init, float d_sub, float scale2, bool drop, uint32_t dctr, const AttnArgs& a, int l15, int grp) {
+    f32x4_t sa = {s_init, s_init, s_init, s_init}, da = {d_init, d_init, d_init, d_init};
+#pragma unroll
+    for (int j = 0; j < DH / 32; ++j) sa = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows<DH>(Ks, 16 * t + l15, 4 * j + grp), qf[j], sa, 0, 0, 0);
+#pragma unroll
+    for (int j = 0; j < DH / 32; ++j) da = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows<DH>(Vs, 16 * t + l15, 4 * j + grp), df[j], da, 0, 0, 0);
+    const float4 bias = *reinterpret_cast<const float4*>(kb + 16 * t + 4 * grp);
+    const float bb[4] = {bias.x, bias.y, bias.z, bias.w};
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const float p = EXP2F(__builtin_fmaf(sa[r], scale2, bb[r]));  // masked key: bias = -inf -> p = 0
+        float dp = da[r];
+        if (drop) dp = DROPOUT_KEEP(dctr + r, a.drop_seed, a.drop_thr) ? dp * a.drop_scale : 0.f;
+        ds[r] = p * (dp - d_sub);
+    }
+}
+// -lse (in units of the raw score) and -D of the queries [q0, q0 + nv) of (b, h) -> rows [0, n_pad) of lse_s / dsum_s; padding queries: -inf / 0, i.e. p = 0
+template <int DH>
+__device__ __forceinline__ void stage_query_stats(float* lse_s, float* dsum_s, const AttnArgs& a, int b, int h, const bf16_t* dobase, long lddo, const bf16_t* obase, long ldo,
+                                                  int q0, int nv, int n_pad, int tid) {
+    for (int i = tid; i < n_pad; i += ATTN_THREADS) {
+        float d = 0.f, l = INFINITY;
+        if (i < nv) {
+            l = a.lse[((long)b * a.heads + h) * a.Nq + q0 + i];
+            l = l == -INFINITY ? INFINITY : l / a.scale;  // fully masked query: -inf -> p = 0
+#pragma unroll
+            for (int v = 0; v < DH / 8; ++v) {
+                float x[8], y[8];
+                ld8<bf16_t>(dobase + (long)(q0 + i) * lddo + v * 8, x);
+                ld8<bf16_t>(obase + (long)(q0 + i) * ldo + v * 8, y);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) d += x[e] * y[e];
+            }
+        }
+        lse_s[i] = -l;
+        dsum_s[i] = -d;   // (both negated: accumulator start values)
+    }
+}
+// P (dropped: what dV contracts) and dS (of the softmax probabilities: what dK contracts) of the 16-query tile at row q0 of the Q / dO tiles in LDS for the wave's 16
+// keys (lane: key l15 = global key krow, queries q0 + 4 grp + r).  D_IN_ACC: dP starts from -D, else -D is added behind the dropout; qq: the global index of query r = 0.
+template <int DH, bool D_IN_ACC>
+__device__ __forceinline__ void bwd_k_tile(float (&p)[4], float (&ds)[4], const char* Qs, const char* Ds, const float* lse_s, const float* dsum_s, int q0,
+                                           const bf16x8_t (&kf)[DH / 32], const bf16x8_t (&vf)[DH / 32], float kbias, float scale2, bool drop, int qq, int krow,
+                                           const AttnArgs& a, int b, int h, int l15, int grp) {
+    const float4 l4 = *reinterpret_cast<const float4*>(lse_s + q0 + 4 * grp);
+    const float4 d4 = *reinterpret_cast<const float4*>(dsum_s + q0 + 4 * grp);
+    const float dd[4] = {d4.x, d4.y, d4.z, d4.w};
+    f32x4_t sa = {l4.x, l4.y, l4.z, l4.w}, da = {0.f, 0.f, 0.f, 0.f};
+    if (D_IN_ACC) da = (f32x4_t){d4.x, d4.y, d4.z, d4.w};
+#pragma unroll
+    for (int j = 0; j < DH / 32; ++j) sa = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows<DH>(Qs, q0 + l15, 4 * j + grp), kf[j], sa, 0, 0, 0);
+#pragma unroll
+    for (int j = 0; j < DH / 32; ++j) da = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows<DH>(Ds, q0 + l15, 4 * j + grp), vf[j], da, 0, 0, 0);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const float pr = EXP2F(__builtin_fmaf(sa[r], scale2, kbias));  // masked / padding key or query: -inf -> 0
+        float pd = pr, dp = da[r];
+        if (drop) {
+            const bool keep = DROPOUT_KEEP((uint32_t)((((long)b * a.heads + h) * a.Nq + (qq + r < a.Nq ? qq + r : a.Nq - 1)) * a.Nk) + krow, a.drop_seed, a.drop_thr);
+            pd = keep ? pr * a.drop_scale : 0.f;
+            dp = keep ? dp * a.drop_scale : 0.f;
+        }
+        p[r] = pd;
+        ds[r] = D_IN_ACC ? pr * dp : pr * (dp + dd[r]);
+    }
+}
 
 // ---- forward ----------------------------------------------------------------------------------------
 // DROP: attention-probability dropout compiled in (a separate instantiation: the mask arithmetic in the inner loops costs registers
@@ -202,6 +297,16 @@ __device__ __forceinline__ void store_rows_paired(bf16_t* rowp, uint2 (&w)[NDT],
             else { *reinterpret_cast<uint2*>(p) = w[2 * k]; *reinterpret_cast<uint2*>(p + 4) = w[2 * k + 1]; }
         }
     }
+}
+// the wave's 16 keys of dV and of scale x dK (lane: key row krow, stored where `valid`) -> their rows; every lane of the wave must call it
+template <int DH>
+__device__ __forceinline__ void store_dk_dv(const AttnArgs& a, const f32x4_t (&dk)[DH / 16], const f32x4_t (&dv)[DH / 16], int b, int h, int krow, bool valid, int lane, int grp) {
+    uint2 vw[DH / 16], kw[DH / 16];
+#pragma unroll
+    for (int dt = 0; dt < DH / 16; ++dt) { vw[dt] = pack_acc(dv[dt], 1.f); kw[dt] = pack_acc(dk[dt], a.scale); }
+    const bool al16 = !(a.lddk & 7) && !(a.lddv & 7) && !((uintptr_t)a.dk & 15) && !((uintptr_t)a.dv & 15);
+    store_rows_paired<DH / 16>(a.dv + ((long)b * a.Nk + krow) * a.lddv + h * DH, vw, lane, grp, valid, al16);
+    store_rows_paired<DH / 16>(a.dk + ((long)b * a.Nk + krow) * a.lddk + h * DH, kw, lane, grp, valid, al16);
 }
 
 // ABL (lab library only, TIMING-ONLY, wrong results -- what each part of the forward costs, same box, same process; profiles/r6b_attn_fwd_ablations.txt): 1 the exponential
@@ -564,112 +669,6 @@ __global__ __launch_bounds__(ATTN_THREADS, 4) void attn_fwd32_kernel(const AttnA
 }
 
 // ---- backward 1: dQ (one workgroup per (b, h); K and V token tiles in LDS; waves walk query tiles) ----
-// Head size 64, written out: the same statements as the DH-templated kernel below, but hipcc's schedule of THIS form is the tuned one (the
-// templated form compiles the 96-key variant to 108 VGPRs instead of 60 -- 4 instead of 8 waves per SIMD -- and the text tower's backward
-// ran 10 % slower with it).
-template <int NCH, bool DROP>
-__global__ __launch_bounds__(ATTN_THREADS, 2) void attn_bwd_dq64_kernel(const AttnArgs a) {
-    ANTMMF_DYN_LDS(char, smem);
-    constexpr int NKP = 32 * NCH;
-    char* Ks = smem;
-    char* Vs = smem + NKP * 128;
-    float* kb = reinterpret_cast<float*>(Vs + NKP * 128);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, grp = lane >> 4;
-    const int b = blockIdx.x / a.heads, h = blockIdx.x % a.heads;
-    stage_rows2<64, NKP>(Ks, a.k + (long)b * a.Nk * a.ldk + h * 64, a.ldk, Vs, a.v + (long)b * a.Nk * a.ldv + h * 64, a.ldv, a.Nk, NKP);
-    stage_key_bias(kb, a, b, NKP);
-    __syncthreads();
-
-    const float scale2 = a.scale * LOG2E, inv_scale2 = 1.0f / scale2;
-    const int nqt = (a.Nq + 15) >> 4;
-    const bool dq_al16 = !(a.lddq & 7) && !((uintptr_t)a.dq & 15);
-    // (unlike the forward / dK-dV kernels this one loads its tile operands at the point of use: with a one-tile-ahead prefetch hipcc
-    // hoists the unrolled LDS fragment reads as well and lands at 256 VGPRs + scratch, i.e. 2 waves per SIMD -- measured slower)
-    bf16x8_t nq0 = {}, nq1 = {}, nd0 = {}, nd1 = {};
-    float nlse = 0.f;
-#define DQ_FETCH(QT)                                                                                      \
-    do {                                                                                                  \
-        const int qi_ = (QT) * 16 + l15;                                                                  \
-        const long tok_ = (long)b * a.Nq + (qi_ < a.Nq ? qi_ : a.Nq - 1);                                 \
-        const bf16_t* qp_ = a.q + tok_ * a.ldq + h * 64 + grp * 8;                                        \
-        const bf16_t* dop_ = a.d_o + tok_ * a.lddo + h * 64 + grp * 8;                                    \
-        nq0 = load_frag_global(qp_); nq1 = load_frag_global(qp_ + 32);                                    \
-        nd0 = load_frag_global(dop_); nd1 = load_frag_global(dop_ + 32);                                  \
-        nlse = a.lse[((long)b * a.heads + h) * a.Nq + (qi_ < a.Nq ? qi_ : a.Nq - 1)];                     \
-    } while (0)
-    for (int qt = wave; qt < nqt; qt += ATTN_THREADS / 64) {
-        const int qi = qt * 16 + l15;
-        const int qrow = qi < a.Nq ? qi : a.Nq - 1;
-        DQ_FETCH(qt);
-        const bf16x8_t qf0 = nq0, qf1 = nq1, df0 = nd0, df1 = nd1;
-        const float lse = nlse;
-        // D_q = <dO[q], O[q]> : this lane covers dh 8g..8g+7 and 32+8g..32+8g+7.  (O is fetched here, not a tile ahead: prefetching it
-        // as well pushes the kernel over the 3-waves-per-SIMD register budget; its latency hides behind the first score MFMAs.)
-        const bf16_t* op = a.o + ((long)b * a.Nq + qrow) * a.ldo + h * 64 + grp * 8;
-        float dsum = 0.f;
-        {
-            union { bf16x8_t f; uint4 u; } d0, d1;
-            d0.f = df0; d1.f = df1;
-            const uint4 o0 = *reinterpret_cast<const uint4*>(op), o1 = *reinterpret_cast<const uint4*>(op + 32);
-            const uint32_t dw[8] = {d0.u.x, d0.u.y, d0.u.z, d0.u.w, d1.u.x, d1.u.y, d1.u.z, d1.u.w};
-            const uint32_t ow[8] = {o0.x, o0.y, o0.z, o0.w, o1.x, o1.y, o1.z, o1.w};
-#pragma unroll
-            for (int e = 0; e < 8; ++e) dsum += bf_lo(dw[e]) * bf_lo(ow[e]) + bf_hi(dw[e]) * bf_hi(ow[e]);
-        }
-        dsum = grp_sum(dsum);
-        // fully masked query (lse = -inf): subtracting +inf makes every z = -inf and exp2(z) = 0 without per-element selects
-        const float lse2 = lse == -INFINITY ? INFINITY : lse * LOG2E;
-        // -lse and -D_q are what the score / dP accumulators START from (z = s scale2 + bias - lse2 becomes ONE fused multiply-add behind the MFMAs, dS = p dP'
-        // one multiply): 6.5 instead of 8.5 VALU slots per score.  A fully masked query starts at -inf and stays there: p = 0.
-        const float s_init = -lse2 * inv_scale2, d_init = DROP ? 0.f : -dsum;
-        const uint32_t dbase = (uint32_t)((((long)b * a.heads + h) * a.Nq + qrow) * a.Nk);
-        bf16x8_t dsf[NCH];
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            LDS_FENCE();
-            float ds[2][4];
-#pragma unroll
-            for (int hh = 0; hh < 2; ++hh) {
-                const int t = 2 * c + hh;
-                if (16 * t >= a.Nk) {   // a key tile of pure padding (257 keys: the 18th): dS = 0, no score work
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) ds[hh][r] = 0.f;
-                    continue;
-                }
-                f32x4_t sa = {s_init, s_init, s_init, s_init}, da = {d_init, d_init, d_init, d_init};
-                sa = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows<64>(Ks, 16 * t + l15, grp), qf0, sa, 0, 0, 0);
-                sa = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows<64>(Ks, 16 * t + l15, 4 + grp), qf1, sa, 0, 0, 0);
-                da = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows<64>(Vs, 16 * t + l15, grp), df0, da, 0, 0, 0);
-                da = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows<64>(Vs, 16 * t + l15, 4 + grp), df1, da, 0, 0, 0);
-                const float4 bias = *reinterpret_cast<const float4*>(kb + 16 * t + 4 * grp);
-                const float bb[4] = {bias.x, bias.y, bias.z, bias.w};
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float p = EXP2F(__builtin_fmaf(sa[r], scale2, bb[r]));  // masked key: bias = -inf -> p = 0
-                    float dp = da[r];
-                    if (DROP) dp = (DROPOUT_KEEP(dbase + 16 * t + 4 * grp + r, a.drop_seed, a.drop_thr) ? dp * a.drop_scale : 0.f) - dsum;
-                    ds[hh][r] = p * dp;
-                }
-            }
-            dsf[c] = pack_frag(ds[0], ds[1]);
-        }
-        // request the next tile's operands now: the register-hungry score phase is over, the dQ phase (36 MFMAs) covers the latency
-        uint2 gw[4];
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-            LDS_FENCE();
-            f32x4_t g = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int c = 0; c < NCH; ++c)
-                g = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tokens<64>(Ks, c, dt, grp, l15), dsf[c], g, 0, 0, 0);
-            gw[dt] = make_uint2(pack_bf2(g[0] * a.scale, g[1] * a.scale), pack_bf2(g[2] * a.scale, g[3] * a.scale));
-        }
-        store_rows_paired<4>(a.dq + ((long)b * a.Nq + qrow) * a.lddq + h * 64, gw, lane, grp, qi < a.Nq, dq_al16);
-    }
-}
-#undef DQ_FETCH
-
-// ---- backward 1, any head size (used for 128)
 template <int NCH, bool DROP, int DH>
 __global__ __launch_bounds__(ATTN_THREADS, DH == 64 ? 2 : 1) void attn_bwd_dq_kernel(const AttnArgs a) {
     ANTMMF_DYN_LDS(char, smem);
@@ -686,49 +685,26 @@ __global__ __launch_bounds__(ATTN_THREADS, DH == 64 ? 2 : 1) void attn_bwd_dq_ke
     const float scale2 = a.scale * LOG2E, inv_scale2 = 1.0f / scale2;
     const int nqt = (a.Nq + 15) >> 4;
     const bool dq_al16 = !(a.lddq & 7) && !((uintptr_t)a.dq & 15);
-    // (unlike the forward / dK-dV kernels this one loads its tile operands at the point of use: with a one-tile-ahead prefetch hipcc
-    // hoists the unrolled LDS fragment reads as well and lands at 256 VGPRs + scratch, i.e. 2 waves per SIMD -- measured slower)
-    bf16x8_t nq[KM] = {}, nd[KM] = {};
-    float nlse = 0.f;
-#define DQ_FETCH(QT)                                                                                      \
-    do {                                                                                                  \
-        const int qi_ = (QT) * 16 + l15;                                                                  \
-        const long tok_ = (long)b * a.Nq + (qi_ < a.Nq ? qi_ : a.Nq - 1);                                 \
-        const bf16_t* qp_ = a.q + tok_ * a.ldq + h * DH + grp * 8;                                        \
-        const bf16_t* dop_ = a.d_o + tok_ * a.lddo + h * DH + grp * 8;                                    \
-        _Pragma("unroll") for (int j_ = 0; j_ < KM; ++j_) nq[j_] = load_frag_global(qp_ + 32 * j_);       \
-        _Pragma("unroll") for (int j_ = 0; j_ < KM; ++j_) nd[j_] = load_frag_global(dop_ + 32 * j_);      \
-        nlse = a.lse[((long)b * a.heads + h) * a.Nq + (qi_ < a.Nq ? qi_ : a.Nq - 1)];                     \
-    } while (0)
     for (int qt = wave; qt < nqt; qt += ATTN_THREADS / 64) {
         const int qi = qt * 16 + l15;
         const int qrow = qi < a.Nq ? qi : a.Nq - 1;
-        DQ_FETCH(qt);
+        // (unlike the forward / dK-dV kernels this one loads its tile operands at the point of use: with a one-tile-ahead prefetch hipcc
+        // hoists the unrolled LDS fragment reads as well and lands at 256 VGPRs + scratch, i.e. 2 waves per SIMD -- measured slower)
+        const long tok = (long)b * a.Nq + qrow;
+        const bf16_t* qp = a.q + tok * a.ldq + h * DH + grp * 8;
+        const bf16_t* dop = a.d_o + tok * a.lddo + h * DH + grp * 8;
         bf16x8_t qf[KM], df[KM];
 #pragma unroll
-        for (int j = 0; j < KM; ++j) { qf[j] = nq[j]; df[j] = nd[j]; }
-        const float lse = nlse;
-        // D_q = <dO[q], O[q]> : this lane covers dh 8g..8g+7 of every 32-wide slice.  (O is fetched here, not a tile ahead: prefetching it
-        // as well pushes the kernel over the 3-waves-per-SIMD register budget; its latency hides behind the first score MFMAs.)
-        const bf16_t* op = a.o + ((long)b * a.Nq + qrow) * a.ldo + h * DH + grp * 8;
-        float dsum = 0.f;
-        {
-            uint32_t dw[4 * KM], ow[4 * KM];
+        for (int j = 0; j < KM; ++j) qf[j] = load_frag_global(qp + 32 * j);
 #pragma unroll
-            for (int j = 0; j < KM; ++j) {
-                union { bf16x8_t f; uint4 u; } d0;
-                d0.f = df[j];
-                const uint4 o0 = *reinterpret_cast<const uint4*>(op + 32 * j);
-                dw[4 * j] = d0.u.x; dw[4 * j + 1] = d0.u.y; dw[4 * j + 2] = d0.u.z; dw[4 * j + 3] = d0.u.w;
-                ow[4 * j] = o0.x; ow[4 * j + 1] = o0.y; ow[4 * j + 2] = o0.z; ow[4 * j + 3] = o0.w;
-            }
-#pragma unroll
-            for (int e = 0; e < 4 * KM; ++e) dsum += bf_lo(dw[e]) * bf_lo(ow[e]) + bf_hi(dw[e]) * bf_hi(ow[e]);
-        }
-        dsum = grp_sum(dsum);
-        // fully masked query (lse = -inf): subtracting +inf makes every z = -inf and exp2(z) = 0 without per-element selects
+        for (int j = 0; j < KM; ++j) df[j] = load_frag_global(dop + 32 * j);
+        const float lse = a.lse[((long)b * a.heads + h) * a.Nq + qrow];
+        // D_q = <dO[q], O[q]>.  (O is fetched here, not a tile ahead: prefetching it as well pushes the kernel over the 3-waves-per-SIMD register
+        // budget; its latency hides behind the first score MFMAs.)
+        const float dsum = grp_sum(dot_do_o<KM>(df, a.o + tok * a.ldo + h * DH + grp * 8));
+        // the accumulators start from -lse (+inf for a fully masked query) and, without dropout, from -D_q; with dropout -D_q follows the keep-and-scale
         const float lse2 = lse == -INFINITY ? INFINITY : lse * LOG2E;
-        const float s_init = -lse2 * inv_scale2, d_init = DROP ? 0.f : -dsum;   // (see attn_bwd_dq64_kernel)
+        const float s_init = -lse2 * inv_scale2, d_init = DROP ? 0.f : -dsum, d_sub = DROP ? dsum : 0.f;
         const uint32_t dbase = (uint32_t)((((long)b * a.heads + h) * a.Nq + qrow) * a.Nk);
         bf16x8_t dsf[NCH];
 #pragma unroll
@@ -738,25 +714,12 @@ __global__ __launch_bounds__(ATTN_THREADS, DH == 64 ? 2 : 1) void attn_bwd_dq_ke
 #pragma unroll
             for (int hh = 0; hh < 2; ++hh) {
                 const int t = 2 * c + hh;
-                if (16 * t >= a.Nk) {
+                if (16 * t >= a.Nk) {   // a key tile of pure padding (257 keys: the 18th): dS = 0, no score work
 #pragma unroll
                     for (int r = 0; r < 4; ++r) ds[hh][r] = 0.f;
                     continue;
                 }
-                f32x4_t sa = {s_init, s_init, s_init, s_init}, da = {d_init, d_init, d_init, d_init};
-#pragma unroll
-                for (int j = 0; j < KM; ++j) sa = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows<DH>(Ks, 16 * t + l15, 4 * j + grp), qf[j], sa, 0, 0, 0);
-#pragma unroll
-                for (int j = 0; j < KM; ++j) da = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows<DH>(Vs, 16 * t + l15, 4 * j + grp), df[j], da, 0, 0, 0);
-                const float4 bias = *reinterpret_cast<const float4*>(kb + 16 * t + 4 * grp);
-                const float bb[4] = {bias.x, bias.y, bias.z, bias.w};
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float p = EXP2F(__builtin_fmaf(sa[r], scale2, bb[r]));  // masked key: bias = -inf -> p = 0
-                    float dp = da[r];
-                    if (DROP) dp = (DROPOUT_KEEP(dbase + 16 * t + 4 * grp + r, a.drop_seed, a.drop_thr) ? dp * a.drop_scale : 0.f) - dsum;
-                    ds[hh][r] = p * dp;
-                }
+                bwd_q_tile_ds<DH>(ds[hh], Ks, Vs, kb, t, qf, df, s_init, d_init, d_sub, scale2, DROP, dbase + 16 * t + 4 * grp, a, l15, grp);
             }
             dsf[c] = pack_frag(ds[0], ds[1]);
         }
@@ -768,19 +731,17 @@ __global__ __launch_bounds__(ATTN_THREADS, DH == 64 ? 2 : 1) void attn_bwd_dq_ke
 #pragma unroll
             for (int c = 0; c < NCH; ++c)
                 g = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tokens<DH>(Ks, c, dt, grp, l15), dsf[c], g, 0, 0, 0);
-            gw[dt] = make_uint2(pack_bf2(g[0] * a.scale, g[1] * a.scale), pack_bf2(g[2] * a.scale, g[3] * a.scale));
+            gw[dt] = pack_acc(g, a.scale);
         }
-        store_rows_paired<DT>(a.dq + ((long)b * a.Nq + qrow) * a.lddq + h * DH, gw, lane, grp, qi < a.Nq, dq_al16);
+        store_rows_paired<DT>(a.dq + tok * a.lddq + h * DH, gw, lane, grp, qi < a.Nq, dq_al16);
     }
 }
-
-#undef DQ_FETCH
 
 // ---- backward 2: dK, dV (one workgroup per (b, h); Q and dO token tiles, lse, D in LDS; waves own key tiles) ----
 template <bool DROP, int DH>
 __global__ __launch_bounds__(ATTN_THREADS, DH == 64 ? 2 : 1) void attn_bwd_dkv_kernel(const AttnArgs a, int NQP) {
     ANTMMF_DYN_LDS(char, smem);
-    constexpr int RB = 2 * DH, KM = DH / 32, DT = DH / 16, NS = DH / 8;
+    constexpr int RB = 2 * DH, KM = DH / 32, DT = DH / 16;
     char* Qs = smem;
     char* Ds = Qs + NQP * RB;
     float* lse_s = reinterpret_cast<float*>(Ds + NQP * RB);
@@ -791,28 +752,11 @@ __global__ __launch_bounds__(ATTN_THREADS, DH == 64 ? 2 : 1) void attn_bwd_dkv_k
     const bf16_t* dobase = a.d_o + (long)b * a.Nq * a.lddo + h * DH;
     const bf16_t* obase = a.o + (long)b * a.Nq * a.ldo + h * DH;
     stage_rows2<DH, 288>(Qs, qbase, a.ldq, Ds, dobase, a.lddo, a.Nq, NQP);
-    for (int i = threadIdx.x; i < NQP; i += ATTN_THREADS) {
-        float d = 0.f, l = INFINITY;  // padding queries: p = 0
-        if (i < a.Nq) {
-            l = a.lse[((long)b * a.heads + h) * a.Nq + i];
-            l = l == -INFINITY ? INFINITY : l / a.scale;  // lse in units of the raw score (what the score accumulators start from, negated); fully masked query: -inf -> p = 0
-#pragma unroll
-            for (int v = 0; v < NS; ++v) {
-                float x[8], y[8];
-                ld8<bf16_t>(dobase + (long)i * a.lddo + v * 8, x);
-                ld8<bf16_t>(obase + (long)i * a.ldo + v * 8, y);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) d += x[e] * y[e];
-            }
-        }
-        lse_s[i] = -l;
-        dsum_s[i] = -d;   // (both negated: accumulator start values)
-    }
+    stage_query_stats<DH>(lse_s, dsum_s, a, b, h, dobase, a.lddo, obase, a.ldo, 0, a.Nq, NQP, threadIdx.x);
     __syncthreads();
 
     const float scale2 = a.scale * LOG2E;
     const int nkt = (a.Nk + 15) >> 4, nqc = NQP >> 5;
-    const bool dkv_al16 = !(a.lddk & 7) && !(a.lddv & 7) && !((uintptr_t)a.dk & 15) && !((uintptr_t)a.dv & 15);
     // (K / V fragments are loaded at the point of use: a one-tile-ahead prefetch costs 34 VGPRs here -- 128 -> 162, one resident wave
     // per SIMD less -- and measured 11 % slower)
     for (int kt = wave; kt < nkt; kt += ATTN_THREADS / 64) {
@@ -837,30 +781,7 @@ __global__ __launch_bounds__(ATTN_THREADS, DH == 64 ? 2 : 1) void attn_bwd_dkv_k
                     for (int r = 0; r < 4; ++r) { p[hh][r] = 0.f; ds[hh][r] = 0.f; }
                     continue;
                 }
-                // lane holds (key = l15, q = q0 + 4g + r); the accumulators start from -lse (in raw-score units) and -D_q of their queries: the exponent is one
-                // fused multiply-add behind the MFMAs, dS one multiply (see attn_bwd_dq64_kernel)
-                const float4 l4 = *reinterpret_cast<const float4*>(lse_s + q0 + 4 * grp);
-                const float4 d4 = *reinterpret_cast<const float4*>(dsum_s + q0 + 4 * grp);
-                const float dd[4] = {d4.x, d4.y, d4.z, d4.w};
-                f32x4_t sa = {l4.x, l4.y, l4.z, l4.w}, da = {0.f, 0.f, 0.f, 0.f};
-                if (!DROP) da = (f32x4_t){d4.x, d4.y, d4.z, d4.w};
-#pragma unroll
-                for (int j = 0; j < KM; ++j) sa = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows<DH>(Qs, q0 + l15, 4 * j + grp), kf[j], sa, 0, 0, 0);
-#pragma unroll
-                for (int j = 0; j < KM; ++j) da = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows<DH>(Ds, q0 + l15, 4 * j + grp), vf[j], da, 0, 0, 0);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float pr = EXP2F(__builtin_fmaf(sa[r], scale2, kbias));  // masked / padding key or query: -inf -> 0
-                    float pd = pr, dp = da[r];
-                    if (DROP) {
-                        const int qq = q0 + 4 * grp + r;
-                        const bool keep = DROPOUT_KEEP((uint32_t)((((long)b * a.heads + h) * a.Nq + (qq < a.Nq ? qq : a.Nq - 1)) * a.Nk) + krow, a.drop_seed, a.drop_thr);
-                        pd = keep ? pr * a.drop_scale : 0.f;
-                        dp = (keep ? dp * a.drop_scale : 0.f) + dd[r];
-                    }
-                    p[hh][r] = pd;                     // dV uses the dropped probabilities
-                    ds[hh][r] = pr * dp;               // dS uses the softmax probabilities
-                }
+                bwd_k_tile<DH, !DROP>(p[hh], ds[hh], Qs, Ds, lse_s, dsum_s, q0, kf, vf, kbias, scale2, DROP, q0 + 4 * grp, krow, a, b, h, l15, grp);
             }
             const bf16x8_t pf = pack_frag(p[0], p[1]), dsf = pack_frag(ds[0], ds[1]);
 #pragma unroll
@@ -869,16 +790,7 @@ __global__ __launch_bounds__(ATTN_THREADS, DH == 64 ? 2 : 1) void attn_bwd_dkv_k
                 dk[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tokens<DH>(Qs, c, dt, grp, l15), dsf, dk[dt], 0, 0, 0);
             }
         }
-        {
-            uint2 vw[DT], kw[DT];
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt) {
-                vw[dt] = make_uint2(pack_bf2(dv[dt][0], dv[dt][1]), pack_bf2(dv[dt][2], dv[dt][3]));
-                kw[dt] = make_uint2(pack_bf2(dk[dt][0] * a.scale, dk[dt][1] * a.scale), pack_bf2(dk[dt][2] * a.scale, dk[dt][3] * a.scale));
-            }
-            store_rows_paired<DT>(a.dv + ((long)b * a.Nk + krow) * a.lddv + h * DH, vw, lane, grp, ki < a.Nk, dkv_al16);
-            store_rows_paired<DT>(a.dk + ((long)b * a.Nk + krow) * a.lddk + h * DH, kw, lane, grp, ki < a.Nk, dkv_al16);
-        }
+        store_dk_dv<DH>(a, dk, dv, b, h, krow, ki < a.Nk, lane, grp);
     }
 }
 
@@ -1027,27 +939,16 @@ __global__ __launch_bounds__(ATTN_THREADS, DH == 64 ? 4 : 2) void attn_bwd_dq_st
     const int qrow = qi < a.Nq ? qi : a.Nq - 1;
     const long tok = (long)b * a.Nq + qrow;
     bf16x8_t qf[KM], df[KM];
-    float dsum = 0.f;   // D_q = <dO[q], O[q]>: this lane covers dh 8g..8g+7 of every 32-wide slice
     {
         const bf16_t* qp = a.q + tok * a.ldq + h * DH + grp * 8;
         const bf16_t* dop = a.d_o + tok * a.lddo + h * DH + grp * 8;
-        const bf16_t* op = a.o + tok * a.ldo + h * DH + grp * 8;
 #pragma unroll
-        for (int j = 0; j < KM; ++j) {
-            qf[j] = load_frag_global(qp + 32 * j);
-            df[j] = load_frag_global(dop + 32 * j);
-            union { bf16x8_t f; uint4 u; } d0;
-            d0.f = df[j];
-            const uint4 o0 = *reinterpret_cast<const uint4*>(op + 32 * j);
-            const uint32_t dw[4] = {d0.u.x, d0.u.y, d0.u.z, d0.u.w}, ow[4] = {o0.x, o0.y, o0.z, o0.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) dsum += bf_lo(dw[e]) * bf_lo(ow[e]) + bf_hi(dw[e]) * bf_hi(ow[e]);
-        }
+        for (int j = 0; j < KM; ++j) { qf[j] = load_frag_global(qp + 32 * j); df[j] = load_frag_global(dop + 32 * j); }
     }
-    dsum = grp_sum(dsum);
+    const float dsum = grp_sum(dot_do_o<KM>(df, a.o + tok * a.ldo + h * DH + grp * 8));   // D_q = <dO[q], O[q]>
     const float lse = a.lse[((long)b * a.heads + h) * a.Nq + qrow];
     const float scale2 = a.scale * LOG2E, inv_scale2 = 1.0f / scale2;
-    // fully masked query (lse = -inf): subtracting +inf makes every exponent -inf and every p = 0 (see attn_bwd_dq64_kernel; the score accumulators start from -lse)
+    // the score accumulators start from -lse (+inf for a fully masked query: p = 0); dP starts from 0 and D_q is subtracted behind the run-time dropout
     const float s_init = -(lse == -INFINITY ? INFINITY : lse * LOG2E) * inv_scale2;
     const uint32_t dbase = (uint32_t)((((long)b * a.heads + h) * a.Nq + qrow) * a.Nk);
     f32x4_t g[DT];
@@ -1074,20 +975,7 @@ __global__ __launch_bounds__(ATTN_THREADS, DH == 64 ? 4 : 2) void attn_bwd_dq_st
                     for (int r = 0; r < 4; ++r) ds[hh][r] = 0.f;
                     continue;
                 }
-                f32x4_t sa = {s_init, s_init, s_init, s_init}, da = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int j = 0; j < KM; ++j) sa = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows<DH>(Ks, 16 * t + l15, 4 * j + grp), qf[j], sa, 0, 0, 0);
-#pragma unroll
-                for (int j = 0; j < KM; ++j) da = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows<DH>(Vs, 16 * t + l15, 4 * j + grp), df[j], da, 0, 0, 0);
-                const float4 bias = *reinterpret_cast<const float4*>(kb + 16 * t + 4 * grp);
-                const float bb[4] = {bias.x, bias.y, bias.z, bias.w};
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float p = EXP2F(__builtin_fmaf(sa[r], scale2, bb[r]));  // masked key: bias = -inf -> p = 0
-                    float dp = da[r];
-                    if (a.drop_thr) dp = DROPOUT_KEEP(dbase + k0 + 16 * t + 4 * grp + r, a.drop_seed, a.drop_thr) ? dp * a.drop_scale : 0.f;
-                    ds[hh][r] = p * (dp - dsum);
-                }
+                bwd_q_tile_ds<DH>(ds[hh], Ks, Vs, kb, t, qf, df, s_init, 0.f, dsum, scale2, a.drop_thr != 0, dbase + k0 + 16 * t + 4 * grp, a, l15, grp);
             }
             const bf16x8_t dsf = pack_frag(ds[0], ds[1]);
 #pragma unroll
@@ -1097,7 +985,7 @@ __global__ __launch_bounds__(ATTN_THREADS, DH == 64 ? 4 : 2) void attn_bwd_dq_st
     if (!wave_on) return;
     uint2 gw[DT];
 #pragma unroll
-    for (int dt = 0; dt < DT; ++dt) gw[dt] = make_uint2(pack_bf2(g[dt][0] * a.scale, g[dt][1] * a.scale), pack_bf2(g[dt][2] * a.scale, g[dt][3] * a.scale));
+    for (int dt = 0; dt < DT; ++dt) gw[dt] = pack_acc(g[dt], a.scale);
     const bool dq_al16 = !(a.lddq & 7) && !((uintptr_t)a.dq & 15);
     store_rows_paired<DT>(a.dq + tok * a.lddq + h * DH, gw, lane, grp, qi < a.Nq, dq_al16);
 }
@@ -1105,7 +993,7 @@ __global__ __launch_bounds__(ATTN_THREADS, DH == 64 ? 4 : 2) void attn_bwd_dq_st
 template <int DH>
 __global__ __launch_bounds__(ATTN_THREADS, DH == 64 ? 4 : 2) void attn_bwd_dkv_stream_kernel(const AttnArgs a, int nkb) {
     ANTMMF_DYN_LDS(char, smem);
-    constexpr int QBS = ATTN_STREAM_KEYS(DH), RB = 2 * DH, KM = DH / 32, DT = DH / 16, NS = DH / 8;   // QBS: queries per staged block
+    constexpr int QBS = ATTN_STREAM_KEYS(DH), RB = 2 * DH, KM = DH / 32, DT = DH / 16;   // QBS: queries per staged block
     char* Qs = smem;
     char* Ds = Qs + QBS * RB;
     float* lse_s = reinterpret_cast<float*>(Ds + QBS * RB);
@@ -1136,23 +1024,7 @@ __global__ __launch_bounds__(ATTN_THREADS, DH == 64 ? 4 : 2) void attn_bwd_dkv_s
         if (qb0) __syncthreads();
         const long ldq = ATTN_PER_BLOCK(a.ldq), lddo = ATTN_PER_BLOCK(a.lddo), ldo = ATTN_PER_BLOCK(a.ldo);
         stage_rows2<DH, QBS>(Qs, qbase + (long)qb0 * ldq, ldq, Ds, dobase + (long)qb0 * lddo, lddo, nv, npad, tid);
-        for (int i = tid; i < npad; i += ATTN_THREADS) {
-            float d = 0.f, l = INFINITY;  // padding queries: p = 0
-            if (i < nv) {
-                l = a.lse[((long)b * a.heads + h) * a.Nq + qb0 + i];
-                l = l == -INFINITY ? INFINITY : l / a.scale;  // lse in units of the raw score, negated below: what the score accumulators start from (fully masked query: p = 0)
-#pragma unroll
-                for (int v = 0; v < NS; ++v) {
-                    float x[8], y[8];
-                    ld8<bf16_t>(dobase + (long)(qb0 + i) * lddo + v * 8, x);
-                    ld8<bf16_t>(obase + (long)(qb0 + i) * ldo + v * 8, y);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) d += x[e] * y[e];
-                }
-            }
-            lse_s[i] = -l;
-            dsum_s[i] = -d;
-        }
+        stage_query_stats<DH>(lse_s, dsum_s, a, b, h, dobase, lddo, obase, ldo, qb0, nv, npad, tid);
         __syncthreads();
         if (!wave_on) continue;
         const int nqc = npad >> 5;
@@ -1166,28 +1038,7 @@ __global__ __launch_bounds__(ATTN_THREADS, DH == 64 ? 4 : 2) void attn_bwd_dkv_s
                     for (int r = 0; r < 4; ++r) { p[hh][r] = 0.f; ds[hh][r] = 0.f; }
                     continue;
                 }
-                // lane holds (key = l15, q = qb0 + q0 + 4g + r); accumulators start from -lse (raw-score units), see attn_bwd_dkv_kernel
-                const float4 l4 = *reinterpret_cast<const float4*>(lse_s + q0 + 4 * grp);
-                const float4 d4 = *reinterpret_cast<const float4*>(dsum_s + q0 + 4 * grp);
-                const float dd[4] = {d4.x, d4.y, d4.z, d4.w};
-                f32x4_t sa = {l4.x, l4.y, l4.z, l4.w}, da = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int j = 0; j < KM; ++j) sa = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows<DH>(Qs, q0 + l15, 4 * j + grp), kf[j], sa, 0, 0, 0);
-#pragma unroll
-                for (int j = 0; j < KM; ++j) da = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows<DH>(Ds, q0 + l15, 4 * j + grp), vf[j], da, 0, 0, 0);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float pr = EXP2F(__builtin_fmaf(sa[r], scale2, kbias));  // masked / padding key or query: -inf -> 0
-                    float pd = pr, dp = da[r];
-                    if (a.drop_thr) {
-                        const int qq = qb0 + q0 + 4 * grp + r;
-                        const bool keep = DROPOUT_KEEP((uint32_t)((((long)b * a.heads + h) * a.Nq + (qq < a.Nq ? qq : a.Nq - 1)) * a.Nk) + krow, a.drop_seed, a.drop_thr);
-                        pd = keep ? pr * a.drop_scale : 0.f;
-                        dp = keep ? dp * a.drop_scale : 0.f;
-                    }
-                    p[hh][r] = pd;                     // dV uses the dropped probabilities
-                    ds[hh][r] = pr * (dp + dd[r]);     // dS uses the softmax probabilities
-                }
+                bwd_k_tile<DH, false>(p[hh], ds[hh], Qs, Ds, lse_s, dsum_s, q0, kf, vf, kbias, scale2, a.drop_thr != 0, qb0 + q0 + 4 * grp, krow, a, b, h, l15, grp);
             }
             const bf16x8_t pf = pack_frag(p[0], p[1]), dsf = pack_frag(ds[0], ds[1]);
 #pragma unroll
@@ -1198,15 +1049,7 @@ __global__ __launch_bounds__(ATTN_THREADS, DH == 64 ? 4 : 2) void attn_bwd_dkv_s
         }
     }
     if (!wave_on) return;
-    uint2 vw[DT], kw[DT];
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) {
-        vw[dt] = make_uint2(pack_bf2(dv[dt][0], dv[dt][1]), pack_bf2(dv[dt][2], dv[dt][3]));
-        kw[dt] = make_uint2(pack_bf2(dk[dt][0] * a.scale, dk[dt][1] * a.scale), pack_bf2(dk[dt][2] * a.scale, dk[dt][3] * a.scale));
-    }
-    const bool dkv_al16 = !(a.lddk & 7) && !(a.lddv & 7) && !((uintptr_t)a.dk & 15) && !((uintptr_t)a.dv & 15);
-    store_rows_paired<DT>(a.dv + ((long)b * a.Nk + krow) * a.lddv + h * DH, vw, lane, grp, ki < a.Nk, dkv_al16);
-    store_rows_paired<DT>(a.dk + ((long)b * a.Nk + krow) * a.lddk + h * DH, kw, lane, grp, ki < a.Nk, dkv_al16);
+    store_dk_dv<DH>(a, dk, dv, b, h, krow, ki < a.Nk, lane, grp);
 }
 
 // ---- backward in ONE kernel (head size 64, 32 < Nk <= 272, no dropout: every tower of the contrastive step) --------------------------------------------------
@@ -1966,8 +1809,7 @@ static int attn_bwd_launch(const AttnArgs& a, hipStream_t stream) {
             return antmmf_check_launch();
         }
     }
-#define BWDQ(N) do { if constexpr (DH == 64) { if (a.drop_thr) ATTN_LAUNCH((attn_bwd_dq64_kernel<N, true>), p.grid, p.lds, stream, a); else ATTN_LAUNCH((attn_bwd_dq64_kernel<N, false>), p.grid, p.lds, stream, a); } \
-        else { if (a.drop_thr) ATTN_LAUNCH((attn_bwd_dq_kernel<N, true, DH>), p.grid, p.lds, stream, a); else ATTN_LAUNCH((attn_bwd_dq_kernel<N, false, DH>), p.grid, p.lds, stream, a); } } while (0)
+#define BWDQ(N) do { if (a.drop_thr) ATTN_LAUNCH((attn_bwd_dq_kernel<N, true, DH>), p.grid, p.lds, stream, a); else ATTN_LAUNCH((attn_bwd_dq_kernel<N, false, DH>), p.grid, p.lds, stream, a); } while (0)
     switch (p.nch) { case 1: BWDQ(1); break; case 3: BWDQ(3); break; case 7: BWDQ(7); break; default: BWDQ(9); break; }
 #undef BWDQ
     const int rc = antmmf_check_launch();

@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include <map>
 #include <string>
+#include <system_error>
 #include <barrier>
 #include <cmath>
 #include <cstdint>
@@ -85,8 +86,24 @@ void launch(F&& body, dim3 grid, dim3 block, size_t lds) {
     make_block();
     std::barrier<> gate(nt);
     std::vector<std::thread> th;
+    th.reserve(nt);
+    auto spawn = [&](auto&& fn) {
+        // Thread creation fails with EAGAIN at the user's process limit: eight emulated ranks and the suite's other workers each want 512 threads at once, and an
+        // ordinary user has such a limit.  The exception would destroy the joinable threads already started, i.e. abort the rank (SIGABRT, nothing printed).  The
+        // threads started so far only wait at their first barrier, so wait for room -- a minute at the most -- and say why before giving up.
+        for (int tries = 0;; ++tries) {
+            try { th.emplace_back(fn); return; }
+            catch (const std::system_error& e) {
+                if (e.code() != std::errc::resource_unavailable_try_again || tries >= 6000) {
+                    std::fprintf(stderr, "[emu] cannot start thread %zu of %d of a workgroup: %s\n", th.size(), nt, e.what());
+                    throw;
+                }
+                std::this_thread::sleep_for(std::chrono::milliseconds(10));
+            }
+        }
+    };
     for (int t = 0; t < nt; ++t)
-        th.emplace_back([&, t] {
+        spawn([&, t] {
             for (long bi = 0; bi < nblocks; ++bi) {
                 if (bi > 0) {
                     gate.arrive_and_wait();          // every thread is out of the previous workgroup

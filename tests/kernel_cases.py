@@ -828,6 +828,33 @@ def dropout_keep_np(idx, seed, p):
     return torch.from_numpy((h >= thr))
 
 
+def case_attention_dropout(ops, dev, B, heads, Nq, Nk, head_dim, p):
+    """Attention with probability dropout vs the oracle attention with the same explicit mask (the numpy twin of the counter hash): forward and all three
+    gradients.  Every second batch item keeps 9 keys (additive -10000 on the rest).  -> what the key-importance checks of case_dropout go on with."""
+    import numpy as np
+
+    D = heads * head_dim
+    scale, seed = head_dim ** -0.5, (77 << 32) | 4242
+    qt, kt, vt, d_o = (q(rnd((B, n, D), 510 + i)) for i, n in enumerate((Nq, Nk, Nk, Nq)))
+    lengths = torch.tensor([Nk, 9] * B)[:B]
+    key_bias = torch.zeros(B, Nk).masked_fill(~(torch.arange(Nk)[None, :] < lengths[:, None]), -10000.0)
+    idx = np.arange(B * heads * Nq * Nk).reshape(B, heads, Nq, Nk)
+    mask = dropout_keep_np(idx, seed, p).float() / (1 - p)
+    qr, kr, vr = (t.clone().requires_grad_(True) for t in (qt, kt, vt))
+    s = torch.matmul(oops.split_heads(qr, heads), oops.split_heads(kr, heads).transpose(-1, -2)) * scale + key_bias[:, None, None, :]
+    ref = oops.merge_heads(torch.matmul(torch.softmax(s, -1) * mask, oops.split_heads(vr, heads)))
+    ref.backward(d_o)
+    qd, kd, vd = qt.to(dev, BF), kt.to(dev, BF), vt.to(dev, BF)
+    tag = f"attn.drop[{B},{heads}x{head_dim},{Nq},{Nk}]"
+    o, lse = ops.attention_fwd(qd, kd, vd, heads, scale, key_bias.to(dev), dropout_p=p, dropout_seed=seed)
+    check(tag + ".o", o, ref, 2e-2, 2e-2)
+    dq, dk, dv = ops.attention_bwd(qd, kd, vd, o, lse, d_o.to(dev, BF), heads, scale, key_bias.to(dev), dropout_p=p, dropout_seed=seed)
+    check(tag + ".dq", dq, qr.grad, 3e-2, 3e-2)
+    check(tag + ".dk", dk, kr.grad, 3e-2, 3e-2)
+    check(tag + ".dv", dv, vr.grad, 3e-2, 3e-2)
+    return qd, kd, vd, lse, key_bias, s, mask, scale, seed
+
+
 def case_dropout(ops, dev):
     """dropout_add vs the numpy twin of the mask (exact), keep rate, residual path; attention with probability dropout vs the
     oracle attention with the same explicit mask (forward and all three gradients)."""
@@ -841,25 +868,8 @@ def case_dropout(ops, dev):
     check("dropout.add", ops.dropout_add(x.to(dev), p, seed, residual=r.to(dev)), want, 1e-6, 1e-6)
     check("dropout.bwd", ops.dropout_add(x.to(dev), p, seed), x * keep / (1 - p), 1e-6, 1e-6)
     check("dropout.bf16", ops.dropout_add(q(x).to(dev, BF), p, seed, residual=q(r).to(dev, BF)), q(x) * keep / (1 - p) + q(r), 2e-2, 2e-2)
-    # attention
-    B, heads, N, D = 2, 2, 21, 128
-    scale, pa, seed = 0.125, 0.2, (77 << 32) | 4242
-    qt, kt, vt, d_o = (q(rnd((B, N, D), 510 + i)) for i in range(4))
-    lengths = torch.tensor([N, 9])
-    key_bias = torch.zeros(B, N).masked_fill(~(torch.arange(N)[None, :] < lengths[:, None]), -10000.0)
-    idx = np.arange(B * heads * N * N).reshape(B, heads, N, N)
-    mask = dropout_keep_np(idx, seed, pa).float() / (1 - pa)
-    qr, kr, vr = (t.clone().requires_grad_(True) for t in (qt, kt, vt))
-    s = torch.matmul(oops.split_heads(qr, heads), oops.split_heads(kr, heads).transpose(-1, -2)) * scale + key_bias[:, None, None, :]
-    ref = oops.merge_heads(torch.matmul(torch.softmax(s, -1) * mask, oops.split_heads(vr, heads)))
-    ref.backward(d_o)
-    qd, kd, vd = qt.to(dev, BF), kt.to(dev, BF), vt.to(dev, BF)
-    o, lse = ops.attention_fwd(qd, kd, vd, heads, scale, key_bias.to(dev), dropout_p=pa, dropout_seed=seed)
-    check("attn.drop.o", o, ref, 2e-2, 2e-2)
-    dq, dk, dv = ops.attention_bwd(qd, kd, vd, o, lse, d_o.to(dev, BF), heads, scale, key_bias.to(dev), dropout_p=pa, dropout_seed=seed)
-    check("attn.drop.dq", dq, qr.grad, 3e-2, 3e-2)
-    check("attn.drop.dk", dk, kr.grad, 3e-2, 3e-2)
-    check("attn.drop.dv", dv, vr.grad, 3e-2, 3e-2)
+    B, heads, N, pa = 2, 2, 21, 0.2
+    qd, kd, vd, lse, key_bias, s, mask, scale, seed = case_attention_dropout(ops, dev, B, heads, N, N, 64, pa)
     # key importance = head mean of the (dropped) probabilities summed over the queries (the reduction of `output_attentions` maps, univl_video_base.py:138-143),
     # accumulated into the caller's buffer: with the same dropout mask, and without dropout
     imp = torch.full((B, N), 0.5, device=dev)

@@ -125,7 +125,7 @@ def test_product_kernel_resources():
     # (name, max VGPRs): 512-thread GEMM workgroups run 2 waves per SIMD -> <= 256; the 8-wave attention workgroups 2 per CU -> <= 128 (the one-kernel backward: 1 per CU -> <= 256)
     must = [("gemm_nt_k64r_kernel<0, 0>", 240), ("gemm_nt_k64r_kernel<1, 0>", 240), ("gemm_nt_k64r_kernel<2, 0>", 240), ("gemm_nt_k64r_kernel<3, 0>", 240),
             ("gemm_nt_k64r_kernel<5, 0>", 256), ("gemm_nt_k64r_kernel<37, 0>", 240), ("gemm_nt_k64r_kernel<69, 0>", 240), ("gemm_nt_k64r_kernel<8, 0>", 248), ("gemm_nt_k64r_kernel<10, 0>", 256), ("gemm_tn_k64_kernel<1>", 256), ("gemm_nt_k64p_kernel<8, 37>", 256), ("gemm_nt_k64p_kernel<9, 37>", 256),
-            ("attn_fwd_kernel<9, false, 64, 0>", 128), ("attn_fwd_kernel<3, false, 64, 0>", 128), ("attn_bwd_dq64_kernel<9, false>", 128), ("attn_bwd_dq64_kernel<3, false>", 128),
+            ("attn_fwd_kernel<9, false, 64, 0>", 128), ("attn_fwd_kernel<3, false, 64, 0>", 128), ("attn_bwd_dq_kernel<9, false, 64>", 128), ("attn_bwd_dq_kernel<3, false, 64>", 128),
             ("attn_bwd_dkv_kernel<false, 64>", 128),
             ("attn_bwd_fused64_kernel<8, true, true, 9, true, 0, false, 0>", 256), ("attn_bwd_fused64_kernel<7, false, false, 0, true, 0, false, 0>", 256),
             ("attn_bwd_fused64_kernel<3, false, false, 0, true, 0, true, 0>", 256),   # one 8-wave workgroup per CU (151 KB of LDS)

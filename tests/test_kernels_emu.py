@@ -360,6 +360,12 @@ def test_dropout_masks(ops):
     kc.case_dropout(ops, DEV)
 
 
+@pytest.mark.parametrize("Nq,Nk", [(33, 33), (21, 97)])
+def test_attention_dropout(ops, Nq, Nk):
+    """The dropout forms of the whole-row backward beyond one key chunk (3 and 7 chunks of 32 keys), self and cross lengths."""
+    kc.case_attention_dropout(ops, DEV, 1, 1, Nq, Nk, 64, 0.2)
+
+
 def test_milnce(ops):
     kc.case_milnce(ops, DEV, Bg=6, n=2, world=2)
     kc.case_milnce(ops, DEV, Bg=4, n=1, world=1)

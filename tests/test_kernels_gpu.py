@@ -279,6 +279,9 @@ def test_gemm_persistent_uneven_rounds(ops):
     dict(B=2, heads=2, Nq=20, Nk=256, bias_kind="none", packed=False),
     dict(B=2, heads=2, Nq=288, Nk=272, bias_kind="inf", packed=False),
     dict(B=2, heads=2, Nq=64, Nk=129, bias_kind="none", packed=False),
+    # the two-kernel backward without dropout beyond the one-kernel form's 272 keys (head size 64: reached for <= 32 and 273 ... 288 keys only)
+    dict(B=1, heads=2, Nq=40, Nk=273, bias_kind="bert", packed=False),
+    dict(B=1, heads=2, Nq=288, Nk=288, bias_kind="inf"),
 ])
 def test_attention(ops, cfg):
     kc.case_attention(ops, DEV, **cfg)
@@ -457,6 +460,13 @@ def test_m2_eval_retrieval(ops, golden, tmp_path):
 
 def test_dropout_masks(ops):
     kc.case_dropout(ops, DEV)
+
+
+# the dropout forms of the whole-row backward: head size 64 at the first key count of 3, 7 and 9 key chunks of 32 (33, 97, 225: the last leaves three key tiles of
+# pure padding) and at all 18 tiles, cross lengths (a swapped Nq / Nk in the dropout counter), head size 128.  (Streamed: test_attn_long_gpu.py::test_dropout, 289 x 289.)
+@pytest.mark.parametrize("Nq,Nk,head_dim", [(33, 33, 64), (97, 97, 64), (225, 225, 64), (288, 288, 64), (21, 97, 64), (97, 97, 128)])
+def test_attention_dropout(ops, Nq, Nk, head_dim):
+    kc.case_attention_dropout(ops, DEV, 1, 2, Nq, Nk, head_dim, 0.2)
 
 
 def test_milnce(ops):
